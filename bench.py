@@ -2,6 +2,8 @@
 """bench.py - edges/sec of a SchNet forward on QM9-shaped synthetic batches (BASELINE.json metric).
 
     python bench.py --gpus N --steps K --warmup W            (N > 1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py ... --full                                (also every side measurement listed below)
+    python bench.py ... --dump-outputs DIR                    (predictions of the last timed step -> DIR/predictions.npy)
 
 A step = one forward of ``gcnn_keras_amd.literature.Schnet.make_model`` (the mirror of kgcnn.literature.Schnet.make_model:
 F=128, depth 3, Gauss(20, 4.0, 0.4), sum pooling) on ONE 128-graph batch whose raw API inputs (float node numbers, float32
@@ -19,19 +21,20 @@ Workloads (``--workload``; default ``config2`` at N = 1 and ``config4`` at N > 1
   (``model.fused.call_group``; every member gets the rows a forward of its own gives), and ``--in-flight`` (default 4) such
   groups overlap on their own HIP streams.  Exactly K forwards run inside the timed region: K // group group launches + K %
   group single ``model(inputs)`` calls.  ``--group 1`` is round 2's mode (every batch its own ``model(inputs)`` call, four in
-  flight); ``single_forward_latency_ms`` reports the latency of a lone ``model(inputs)`` call beside the throughput, and
-  ``stream_fresh_batches`` the rate for batches that are seen ONCE (bind + direct launch, no replay).  With N > 1
+  flight); with ``--full``, ``single_forward_latency_ms`` reports the latency of a lone ``model(inputs)`` call beside the
+  throughput, and ``stream_fresh_batches`` the rate for batches that are seen ONCE (bind + direct launch, no replay).  With N > 1
   (``--workload config2``) every rank owns its own 128-graph batches and one all-gather of the (G,1) predictions follows
   every forward: weak scaling.
 * ``config4``  BASELINE config 4: 100 000 QM9-shaped molecules (seed 3456) cut into N contiguous shards balanced by edge
   count (gcnn_keras_amd/sharding.py); rank r builds the edge lists of shard r on its GPU (the engine's SetRange, the
   reference's rule), runs one forward per step on it - no exchange during the forward - and ONE RCCL all-gather returns
-  the (100000,1) predictions in graph order.  Total work is fixed as N grows: strong scaling.  At N = 1 the default run
-  appends this workload's single-GPU rate as ``config4_single_gpu`` (the N = 1 point of that curve).
+  the (100000,1) predictions in graph order.  Total work is fixed as N grows: strong scaling.  At N = 1 a ``--full`` run
+  of the default workload appends this workload's single-GPU rate as ``config4_single_gpu`` (the N = 1 point of that curve).
 
-Prints ONE JSON line (rank 0) with the contract keys plus ``roofline`` (dominant kernel, measured live with HIP events)
-and ``cpu_baseline`` (CPU restatements of the reference's unfused op sequence - C/OpenMP port and torch-CPU - timed on
-the host cores).
+Prints ONE JSON line (rank 0) with the contract keys.  A plain run sets up, warms up, times the K steps, writes the
+outputs (``--dump-outputs``) and prints; ``--full`` adds ``roofline`` (dominant kernel, measured live with HIP events),
+``cpu_baseline`` (CPU restatements of the reference's unfused op sequence - C/OpenMP port and torch-CPU - timed on the
+host cores) and the side measurements above, each after the timed region.
 """
 import argparse
 import json
@@ -241,17 +244,25 @@ class _Dist:
 
 
 def _time_steps(d, step, warmup, steps):
-    """W untimed warm-up steps, then exactly K steps bracketed by barrier + synchronize; MAX over ranks."""
+    """W untimed warm-up steps, then exactly K steps bracketed by barrier + synchronize; MAX over ranks.  Returns the
+    elapsed time and what the last timed step returned."""
     torch = d.torch
     for i in range(warmup):
         step(i)
     d.barrier()
     t0 = time.perf_counter()
     for i in range(steps):
-        step(i)
+        out = step(i)
     torch.cuda.set_stream(torch.cuda.default_stream())
     d.barrier()
-    return d.reduce(time.perf_counter() - t0, "MAX")
+    return d.reduce(time.perf_counter() - t0, "MAX"), out
+
+
+def dump_outputs(directory, arrays):
+    """``--dump-outputs``: every array as ``directory/<name>.npy`` in float32 (host copies taken after the timed region)."""
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), np.asarray(a, dtype=np.float32))
 
 
 # ---------------------------------------------------------------------------------------------------- config 2
@@ -292,42 +303,49 @@ def run_config2(args, d):
 
     def run_steps(n):
         # exactly n forwards of 128-graph batches: n // group launch groups (`group` batches concatenated on the device and
-        # served by one launch sequence, route.call_group), the remainder as single forwards
+        # served by one launch sequence, route.call_group), the remainder as single forwards; returns the last forward's
+        # result
         full, rem = divmod(n, group)
+        out = None
         for j in range(full):
-            fwd.replay_group(j)
+            out = fwd.replay_group(j)
         for r in range(rem):
-            fwd.replay(r, restore_stream=False)
+            out = fwd.replay(r, restore_stream=False)
+        return out[-1] if isinstance(out, list) else out
 
     if group > 1:
         run_steps(args.warmup)
         d.barrier()
         t0 = time.perf_counter()
-        run_steps(args.steps)
+        last = run_steps(args.steps)
         torch.cuda.set_stream(torch.cuda.default_stream())
         d.barrier()
         elapsed = d.reduce(time.perf_counter() - t0, "MAX")
     else:
-        elapsed = _time_steps(d, step, args.warmup, args.steps)
+        elapsed, last = _time_steps(d, step, args.warmup, args.steps)
     total_edges = d.reduce(float(n_edges), "SUM")
     fwd.check_flags()
-    # latency of ONE model(inputs) call with nothing else on the GPU (batch 0 alone), beside the throughput
-    for _ in range(10):
-        fwd.replay(0, restore_stream=False)
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for _ in range(100):
-        fwd.replay(0, restore_stream=False)
-    torch.cuda.synchronize()
-    latency_ms = (time.perf_counter() - t1) / 100 * 1e3
-    torch.cuda.set_stream(torch.cuda.default_stream())
-    roof = fwd.roofline(HBM_PEAK_GBS, FP32_MFMA_PEAK_TF)  # dominant kernel, timed with HIP events on its stream
-    roof.update(pmc_traffic(roof.get("kernel", ""), n_graphs * group))
-    roof.update(pmc_matrix_pipe(roof.get("kernel", ""), n_graphs * group, roof.get("avg_launch_us")))
-    roof["measured"] = ("HIP events on the kernel's stream around back-to-back launches of the kernel alone on the GPU "
-                        "(50 launches per HIP-graph replay, so that the host's call rate is not what is timed), after "
-                        "the timed region; rocprofv3 --kernel-trace --stats of `bench.py --in-flight 1` (profiles/) "
-                        "gives the same average for the kernel inside the forward")
+    if args.dump_outputs and d.rank == 0:
+        dump_outputs(args.dump_outputs, {"predictions": last.cpu().numpy()})   # (G,1) of the last timed forward
+    del last       # a result still held keeps its result-ring buffer from the calls that follow
+    if args.full:
+        # latency of ONE model(inputs) call with nothing else on the GPU (batch 0 alone), beside the throughput
+        for _ in range(10):
+            fwd.replay(0, restore_stream=False)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for _ in range(100):
+            fwd.replay(0, restore_stream=False)
+        torch.cuda.synchronize()
+        latency_ms = (time.perf_counter() - t1) / 100 * 1e3
+        torch.cuda.set_stream(torch.cuda.default_stream())
+        roof = fwd.roofline(HBM_PEAK_GBS, FP32_MFMA_PEAK_TF)  # dominant kernel, timed with HIP events on its stream
+        roof.update(pmc_traffic(roof.get("kernel", ""), n_graphs * group))
+        roof.update(pmc_matrix_pipe(roof.get("kernel", ""), n_graphs * group, roof.get("avg_launch_us")))
+        roof["measured"] = ("HIP events on the kernel's stream around back-to-back launches of the kernel alone on the GPU "
+                            "(50 launches per HIP-graph replay, so that the host's call rate is not what is timed), after "
+                            "the timed region; rocprofv3 --kernel-trace --stats of `bench.py --in-flight 1` (profiles/) "
+                            "gives the same average for the kernel inside the forward")
     if d.rank != 0:
         return None
     ms_per_step = elapsed / args.steps * 1e3
@@ -355,15 +373,16 @@ def run_config2(args, d):
                             "the union - and %d such groups are in flight on their own streams; K steps = K // %d group "
                             "launches + K %% %d single forwards" % (n_graphs, group, slots, group, group)),
                    "sharding": "by graph, 1 all-gather of predictions per step" if world > 1 else "single GPU"},
-        "single_forward_latency_ms": latency_ms,
         "stream_placement": fwd.placement,   # in-flight streams: best of the draws is used; a random draw gives the median
-        "roofline": roof,
         "forward_model": {"hbm_frac": fwd_bytes / (ms_per_step * 1e-3) / (HBM_PEAK_GBS * 1e9),
                           "mfma_frac": fwd_flops / (ms_per_step * 1e-3) / (FP32_MFMA_PEAK_TF * 1e12),
                           "algorithmic_bytes": fwd_bytes, "flops": fwd_flops,
-                          "kernels_per_forward": fwd.num_launches},
+                          "kernels_per_forward": fwd._fused.num_launches if fwd.mode == "fused" else fwd.num_launches},
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full:
+        line["single_forward_latency_ms"] = latency_ms
+        line["roofline"] = roof
+    if args.full and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(batch, params, DEPTH)
     if fwd.model.fused is not None:
         fwd.model.fused.release()
@@ -428,15 +447,19 @@ def run_config4(args, d, standalone=True):
     for i in range(5):
         step(i)
     torch.cuda.synchronize()
-    elapsed = _time_steps(d, step, warmup, steps)
+    elapsed, last = _time_steps(d, step, warmup, steps)
     model.fused.check_flags()
-    full = step(0)
-    torch.cuda.synchronize()
-    assert tuple(full.shape) == (args.total_graphs, 1) and bool(torch.isfinite(full).all())
-    slot = model.fused.slot_of(inputs)
-    roof = slot.roofline(HBM_PEAK_GBS, FP32_MFMA_PEAK_TF, iters=10)
-    roof["measured"] = "HIP events on the kernel's stream around back-to-back launches of the kernel alone, after the timed region"
-    roof.update(pmc_matrix_pipe(roof.get("kernel", ""), n_graphs, roof.get("avg_launch_us")))
+    if standalone and args.dump_outputs and d.rank == 0:
+        dump_outputs(args.dump_outputs, {"predictions": last.cpu().numpy()})   # (total_graphs,1) of the last timed step
+    del last
+    if args.full:
+        full = step(0)
+        torch.cuda.synchronize()
+        assert tuple(full.shape) == (args.total_graphs, 1) and bool(torch.isfinite(full).all())
+        slot = model.fused.slot_of(inputs)
+        roof = slot.roofline(HBM_PEAK_GBS, FP32_MFMA_PEAK_TF, iters=10)
+        roof["measured"] = "HIP events on the kernel's stream around back-to-back launches of the kernel alone, after the timed region"
+        roof.update(pmc_matrix_pipe(roof.get("kernel", ""), n_graphs, roof.get("avg_launch_us")))
     model.fused.release()
     if d.rank != 0:
         return None
@@ -456,14 +479,15 @@ def run_config4(args, d, standalone=True):
                    "api": "gcnn_keras_amd.literature.Schnet.make_model(depth=3)(inputs)",
                    "sharding": ("contiguous graph ranges by edge count, no exchange during the forward, 1 "
                                 "all_gather_into_tensor per step (RCCL)" if world > 1 else "single GPU, no collective")},
-        "roofline": roof,
         "forward_model": {"hbm_frac": fwd_bytes / (ms_per_step * 1e-3) / (HBM_PEAK_GBS * 1e9),
                           "mfma_frac": fwd_flops / (ms_per_step * 1e-3) / (FP32_MFMA_PEAK_TF * 1e12),
                           "algorithmic_bytes_rank0": fwd_bytes, "flops_rank0": fwd_flops},
     }
-    if standalone and world == 1 and not args.no_cpu_baseline:
+    if args.full:
+        line["roofline"] = roof
+    if args.full and standalone and world == 1 and not args.no_cpu_baseline:
         sample = synth.qm9_like_batch(num_graphs=128, seed=3456)   # the first 128 molecules of the same stream
-        line["cpu_baseline"] = cpu_baseline(sample, params, DEPTH)
+        line["cpu_baseline"] = cpu_baseline(sample, synth.schnet_params(seed=7), DEPTH)
     return line
 
 
@@ -607,14 +631,21 @@ def main():
     ap.add_argument("--group", type=int, default=None,
                     help="config2: independent batches served by ONE launch sequence (concatenated on the device, "
                          "route.call_group); 1 = every batch its own model(inputs) call; default 5 (1 when --in-flight is given alone)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: single-call latency, roofline of the dominant "
+                         "kernel, CPU baseline, and (default 1-GPU workload) the fresh-batch rate and config 4 on one GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the predictions of the last timed step to DIR/predictions.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-stream", action="store_true",
-                    help="skip the fresh-batch measurement (64 distinct batches, each called once) appended to the default line")
+                    help="skip the fresh-batch measurement (64 distinct batches, each called once) appended to the --full line")
     ap.add_argument("--no-config4-reference", action="store_true",
-                    help="skip the single-GPU config-4 rate appended to the default 1-GPU line")
+                    help="skip the single-GPU config-4 rate appended to the --full 1-GPU line")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI (production); gloo only rehearses N > 1 on a single-GPU box")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # Several forwards are kept in flight on separate HIP streams (--in-flight).  ROCm multiplexes streams onto a few
     # hardware queues; 8 instead of the default 4 leave room beside the null stream, and SchnetForward.load_batch picks
@@ -632,12 +663,12 @@ def main():
         return
     if workload == "config2":
         line = run_config2(args, d)
-        if line is not None and d.world == 1 and args.workload == "auto" and not args.no_stream:
+        if args.full and line is not None and d.world == 1 and args.workload == "auto" and not args.no_stream:
             fresh = run_stream(args, d)
             fresh["fraction_of_replay_value"] = fresh["edges_per_s_resident"] / line["value"]
             fresh["grouped_fraction_of_replay_value"] = fresh["edges_per_s_resident_grouped"] / line["value"]
             line["stream_fresh_batches"] = fresh
-        if line is not None and d.world == 1 and args.workload == "auto" and not args.no_config4_reference:
+        if args.full and line is not None and d.world == 1 and args.workload == "auto" and not args.no_config4_reference:
             ref = run_config4(args, d, standalone=False)
             line["config4_single_gpu"] = {k: ref[k] for k in ("value", "unit", "ms_per_step", "steps", "scaling")}
             line["config4_single_gpu"]["workload"] = ref["config"]["workload"]

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of cfconv builds for the in-flight bench: MPENGINE_INFLIGHT_CFCONV_FLAGS unset (4-wave) vs 4 (8 waves on one LDS image)
 cd "$GRAFT_REPO_ROOT"
-B="python bench.py --no-cpu-baseline --no-config4-reference"
+B="python bench.py --full --no-cpu-baseline --no-config4-reference"
 show() { python -c "
 import json,sys
 l=json.loads(sys.stdin.read().strip().splitlines()[-1])

@@ -2,7 +2,7 @@
 # A/B of the node-kernel builds for the in-flight bench: bf16-piece images (default, 368 registers: one workgroup per CU)
 # vs FP32 matrix instructions (MPENGINE_NODE_BF16=0: 250 registers for the MID chain, two workgroups per CU)
 cd "$GRAFT_REPO_ROOT"
-B="python bench.py --no-cpu-baseline --no-config4-reference"
+B="python bench.py --full --no-cpu-baseline --no-config4-reference"
 show() { python -c "
 import json,sys
 l=json.loads(sys.stdin.read().strip().splitlines()[-1])

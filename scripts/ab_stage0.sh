@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of two builds of libmpengine.so (MPENGINE_LIB) on one box: rocprofv3 kernel averages of `bench.py --in-flight 1`.
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-B="python3 bench.py --no-cpu-baseline --no-config4-reference --steps 300 --in-flight 1"
+B="python3 bench.py --full --no-cpu-baseline --no-config4-reference --steps 300 --in-flight 1"
 for round in 1 2; do
   for tag in old new; do
     if [ $tag = old ]; then export MPENGINE_LIB=$GRAFT_REPO_ROOT/gcnn_keras_amd/csrc/libmpengine_old.so; else unset MPENGINE_LIB; fi

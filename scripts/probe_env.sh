@@ -1,7 +1,7 @@
 #!/bin/bash
 # Runtime environment knobs against the headline bench (4 batches in flight and one at a time): one JSON summary line each.
 cd "$GRAFT_REPO_ROOT"
-B="python bench.py --no-cpu-baseline --no-config4-reference"
+B="python bench.py --full --no-cpu-baseline --no-config4-reference"
 show() { python -c "
 import json,sys
 l=json.loads(sys.stdin.read().strip().splitlines()[-1])

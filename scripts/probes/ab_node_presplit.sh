@@ -3,7 +3,7 @@
 # libmpengine_old.so (every consuming wave splits the tile): parity tests on the new build, then the bench alternating.
 cd "$GRAFT_REPO_ROOT"
 python -m pytest tests/test_gpu_fused.py tests/test_gpu_schnet.py tests/test_gpu_fullsize.py -x -q 2>&1 | tail -2 || exit 1
-B="python bench.py --no-cpu-baseline --no-config4-reference --no-stream"
+B="python bench.py --full --no-cpu-baseline --no-config4-reference --no-stream"
 show() { python -c "
 import json,sys
 l=json.loads([x for x in sys.stdin.read().strip().splitlines() if x.startswith('{')][-1])

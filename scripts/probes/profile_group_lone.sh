@@ -4,7 +4,7 @@
 # bench line's roofline object times with HIP events.
 set -e
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-B="python3 bench.py --no-cpu-baseline --no-config4-reference --no-stream --steps 300"
+B="python3 bench.py --full --no-cpu-baseline --no-config4-reference --no-stream --steps 300"
 rocprofv3 --kernel-trace --stats -d gpurun_out/p3_grp1 -o b -- $B --group 5 --in-flight 1 > gpurun_out/p3_grp1.log 2>&1
 mkdir -p gpurun_out/stats
 db=$(find gpurun_out/p3_grp1 -name "*_results.db" | head -1)

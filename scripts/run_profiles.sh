@@ -4,7 +4,7 @@
 # scripts/summarize_profiles.py r02.
 set -e
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-B="python3 bench.py --no-cpu-baseline --no-config4-reference --steps 300"
+B="python3 bench.py --full --no-cpu-baseline --no-config4-reference --steps 300"
 rocprofv3 --kernel-trace --stats -d gpurun_out/prof5_c2_1 -o b -- $B --in-flight 1 > gpurun_out/prof5_c2_1.log 2>&1
 rocprofv3 --kernel-trace --stats -d gpurun_out/prof5_c2_4 -o b -- $B > gpurun_out/prof5_c2_4.log 2>&1
 rocprofv3 --kernel-trace --stats -d gpurun_out/prof5_sf -o sf -- python3 scripts/bench_schnet_force.py 64 --profile fork 200 > gpurun_out/prof5_sf.log 2>&1

@@ -3,7 +3,7 @@
 # gpurun_out/stats/*.csv, copied to profiles/r03_*): config 2 lone forward, 4 in flight, launch groups, fresh-batch stream.
 set -e
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-B="python3 bench.py --no-cpu-baseline --no-config4-reference --no-stream --steps 300"
+B="python3 bench.py --full --no-cpu-baseline --no-config4-reference --no-stream --steps 300"
 rocprofv3 --kernel-trace --stats -d gpurun_out/p3_c2_1 -o b -- $B --in-flight 1 > gpurun_out/p3_c2_1.log 2>&1
 rocprofv3 --kernel-trace --stats -d gpurun_out/p3_c2_4 -o b -- $B --group 1 --in-flight 4 > gpurun_out/p3_c2_4.log 2>&1
 rocprofv3 --kernel-trace --stats -d gpurun_out/p3_grp -o b -- $B > gpurun_out/p3_grp.log 2>&1
