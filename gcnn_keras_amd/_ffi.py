@@ -59,6 +59,11 @@ _SIGNATURES = {
     "mp_dense_splitk_workspace_bytes": [c_int64, c_int64, c_int, P],
     "mp_dense_splitk_f32": [P, c_int64, c_int64, P, P, c_int64, c_int, c_float, c_int, P, c_size_t, P, P],
     "mp_activation_f32": [c_int, c_float, P, c_int64, P, P],
+    "mp_dense_wgrad_ws_bytes": [c_int64, c_int64, c_int64, P],
+    "mp_dense_wgrad_f32": [P, c_int64, c_int64, P, c_int64, P, P, P, c_size_t, P],
+    "mp_embedding_grad_ws_bytes": [c_int64, c_int64, P],
+    "mp_embedding_grad_f32": [P, c_int64, P, c_int64, c_int64, P, c_size_t, P, P],
+    "mp_softmax_rows_grad_f32": [P, P, c_int64, c_int64, P, P],
     "mp_softmax_rows_f32": [P, c_int64, c_int64, P, P],
     "mp_binary_f32": [c_int, P, P, P, P, c_int64, c_int64, c_int64, P, P],
     "mp_copy_cols_f32": [P, c_int64, c_int64, P, c_int64, c_int64, c_int64, c_int64, P],

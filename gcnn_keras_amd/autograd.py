@@ -1,9 +1,11 @@
-"""Reverse-mode rules for the engine ops, used only by ``EnergyForceModel`` (kgcnn/model/force.py:159-186).
+"""Reverse-mode rules for the engine ops, used by ``EnergyForceModel`` (kgcnn/model/force.py:159-186) and for training.
 
 ``torch.autograd`` supplies the tape (plumbing); every forward AND backward computation is an engine kernel:
 gather-backward = segment-sum over the CSR of the gathered index column, segment-sum-backward = gather by the receiver
 ids, Dense-backward = Dense with the transposed kernel, plus the elementwise derivative kernels of csrc/mp_backward.hip.
-Only input gradients are produced (forces need dE/dx, not dE/dW).
+Weight gradients (training, ``Model.train_on_batch``) come from csrc/mp_wgrad.hip: dW = x^T g and db = sum_r g for
+Dense, the embedding table gradient, and the reverse of the row softmax.  Each is produced only when
+``ctx.needs_input_grad`` asks for it.
 """
 import torch
 
@@ -12,6 +14,21 @@ from . import _ffi
 
 def needs_grad(*tensors):
     return torch.is_grad_enabled() and any(t is not None and torch.is_tensor(t) and t.requires_grad for t in tensors)
+
+
+def route_weights_need_grad(route):
+    """A fused route reads the weights in place and has no reverse rule for them: in grad mode it steps aside as soon as
+    one of them requires grad (``route._tensors()`` / the cached ``route._wlist`` of ``_sync_weights``)."""
+    if not torch.is_grad_enabled():
+        return False
+    from .layers.base import weight_epoch
+    wl = route._wlist
+    if wl is None or route._wepoch != weight_epoch():
+        wl = [t for t in route._tensors().values() if t is not None]
+    for t in wl:
+        if t.requires_grad:
+            return True
+    return False
 
 
 def _rows_elems(t):
@@ -106,14 +123,31 @@ class PoolGraph(torch.autograd.Function):
         return out, None, None, None
 
 
+def dense_wgrad(x, g, with_bias=True):
+    """``(x^T g, sum_r g)`` over the rows of ``x`` (..., K) and ``g`` (..., U) on ``mp_dense_wgrad_f32``."""
+    import ctypes
+    k, u = int(x.shape[-1]), int(g.shape[-1])
+    xc, gc = x.contiguous(), g.contiguous()
+    rows = xc.numel() // max(k, 1)
+    dw = torch.empty((k, u), dtype=torch.float32, device=g.device)
+    db = torch.empty((u,), dtype=torch.float32, device=g.device) if with_bias else None
+    nbytes = ctypes.c_size_t(0)
+    _ffi.call("mp_dense_wgrad_ws_bytes", rows, k, u, ctypes.byref(nbytes))
+    ws = torch.empty((max(nbytes.value, 4) // 4,), dtype=torch.float32, device=g.device) if nbytes.value else None
+    _ffi.call("mp_dense_wgrad_f32", _ffi.ptr(xc), rows, k, _ffi.ptr(gc), u, _ffi.ptr(dw), _ffi.ptr(db), _ffi.ptr(ws),
+              nbytes.value, _ffi.stream())
+    return dw, db
+
+
 class Dense(torch.autograd.Function):
-    """y = act(x W + b); backward dx = (dy * act'(pre)) W^T."""
+    """y = act(x W + b); backward gp = dy * act'(pre), dx = gp W^T, dW = x^T gp, db = sum_rows gp (each only when asked)."""
 
     @staticmethod
     def forward(ctx, x, kernel, bias, act_code, alpha):
         from .layers.modules import _dense_raw
         pre = _dense_raw(x, kernel, bias, 0, 0.0)
         ctx.kernel, ctx.act, ctx.alpha = kernel, act_code, alpha
+        ctx.x = x if ctx.needs_input_grad[1] else None
         if act_code == 0:
             ctx.pre = None
             return pre
@@ -131,8 +165,66 @@ class Dense(torch.autograd.Function):
             _ffi.call("mp_activation_grad_f32", ctx.act, float(ctx.alpha), _ffi.ptr(ctx.pre), _ffi.ptr(gc), gc.numel(),
                       _ffi.ptr(gp), _ffi.stream())
             gc = gp
-        wt = ctx.kernel.t().contiguous()  # (units, in): layout change only
-        return _dense_raw(gc, wt, None, 0, 0.0), None, None, None, None
+        gx = gw = gb = None
+        if ctx.needs_input_grad[0]:
+            wt = ctx.kernel.t().contiguous()  # (units, in): layout change only
+            gx = _dense_raw(gc, wt, None, 0, 0.0)
+        if ctx.needs_input_grad[1]:
+            gw, gb = dense_wgrad(ctx.x, gc, with_bias=ctx.needs_input_grad[2])
+        elif ctx.needs_input_grad[2]:
+            u = int(gc.shape[-1])
+            gb = torch.empty((u,), dtype=torch.float32, device=gc.device)
+            _ffi.call("mp_sum_axis_f32", _ffi.ptr(gc), 1, gc.numel() // max(u, 1), u, 1, _ffi.ptr(gb), _ffi.stream())
+        return gx, gw, gb, None, None
+
+
+class Embedding(torch.autograd.Function):
+    """Keras Embedding on float node numbers; backward = table gradient (``mp_embedding_grad_f32``)."""
+
+    @staticmethod
+    def forward(ctx, numbers, table):
+        vocab, dim = int(table.shape[0]), int(table.shape[1])
+        n = numbers.numel()
+        out = torch.empty(tuple(numbers.shape) + (dim,), dtype=torch.float32, device=numbers.device)
+        _ffi.call("mp_embedding_f32", _ffi.ptr(table), vocab, dim, _ffi.ptr(numbers), n, _ffi.ptr(out), None,
+                  _ffi.stream())
+        ctx.numbers, ctx.vocab, ctx.dim = numbers, vocab, dim
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        import ctypes
+        gc = g.contiguous()
+        n = ctx.numbers.numel()
+        nbytes = ctypes.c_size_t(0)
+        _ffi.call("mp_embedding_grad_ws_bytes", n, ctx.vocab, ctypes.byref(nbytes))
+        ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=gc.device)
+        out = torch.empty((ctx.vocab, ctx.dim), dtype=torch.float32, device=gc.device)
+        _ffi.call("mp_embedding_grad_f32", _ffi.ptr(ctx.numbers), n, _ffi.ptr(gc), ctx.vocab, ctx.dim, _ffi.ptr(ws),
+                  nbytes.value, _ffi.ptr(out), _ffi.stream())
+        return None, out
+
+
+class Softmax(torch.autograd.Function):
+    """Row softmax on the last axis; backward from the saved output (``mp_softmax_rows_grad_f32``)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        xc = x.contiguous()
+        c = int(xc.shape[-1])
+        out = torch.empty_like(xc)
+        _ffi.call("mp_softmax_rows_f32", _ffi.ptr(xc), xc.numel() // max(c, 1), c, _ffi.ptr(out), _ffi.stream())
+        ctx.y = out
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        gc = g.contiguous()
+        c = int(gc.shape[-1])
+        out = torch.empty_like(gc)
+        _ffi.call("mp_softmax_rows_grad_f32", _ffi.ptr(ctx.y), _ffi.ptr(gc), gc.numel() // max(c, 1), c, _ffi.ptr(out),
+                  _ffi.stream())
+        return out
 
 
 class Activation(torch.autograd.Function):

@@ -296,10 +296,11 @@ class GraphedModel:
     the images) itself: binding more batches than ``max_slots``, or ``route.release()``, cannot free memory the graph
     still uses.  ``__call__`` first lets the route refresh its derived weight layouts (``set_weights`` after the capture
     is picked up: the images are re-filled in place) and raises if weight tensors were REPLACED by other objects - the
-    graph holds the old addresses, capture again.
+    graph holds the old addresses, capture again.  Layer-level images captured on the layer path (``SchNetCFconv``'s
+    packed filter weights) are re-filled in place before each replay in the same way.
     """
 
-    def __init__(self, model, inputs, grad=None):
+    def __init__(self, model, inputs, grad=None, layers=None):
         if not torch.cuda.is_available():
             raise _ffi.EngineError("GraphedModel needs an MI355X (no CPU fallback)")
         if grad is None:
@@ -333,11 +334,30 @@ class GraphedModel:
                         self._pinned.append(next(reversed(table.values())))      # most recently used = this capture's
                 self._pinned.extend(getattr(r, a, None) for a in ("_packed", "_images", "_grad_images", "_p"))
                 self._routes.append((r, self._weight_objects(r)))
+            # layer-level weight images the captured kernels read (SchNetCFconv's packed filter weights)
+            self._layer_images = [lay for lay in self._all_layers(model, layers) if getattr(lay, "_packed", None) is not None
+                            and hasattr(lay, "refresh_packed")]
         finally:
             for r, mode in zip(routes, saved):
                 r.mode = mode
             for m in auto:
                 m.auto_graph = True
+
+    @staticmethod
+    def _all_layers(model, layers):
+        todo = list(layers if layers is not None else getattr(model, "layers", None) or [])
+        energy = getattr(model, "energy_model", None)
+        if layers is None and energy is not None:
+            todo += list(getattr(energy, "layers", None) or [])
+        out, seen = [], set()
+        while todo:
+            lay = todo.pop()
+            if id(lay) in seen or not hasattr(lay, "sublayers"):
+                continue
+            seen.add(id(lay))
+            out.append(lay)
+            todo.extend(lay.sublayers())
+        return out
 
     @staticmethod
     def _weight_objects(route):
@@ -350,6 +370,8 @@ class GraphedModel:
             if self._weight_objects(r) != objects:
                 raise _ffi.EngineError("GraphedModel: weight tensors of the model were replaced after the capture (the graph "
                                        "holds the old addresses); build a new GraphedModel")
+        for lay in self._layer_images:
+            lay.refresh_packed()
         self.graph.replay()
         return self.output
 

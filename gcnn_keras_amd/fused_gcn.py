@@ -216,8 +216,7 @@ class GcnFusedRoute:
             ws += [d.kernel, d.bias]
         return ws
 
-    @staticmethod
-    def accepts(inputs):
+    def accepts(self, inputs):
         from .autograd import needs_grad
         from .ragged import RaggedTensor
         if not (isinstance(inputs, (list, tuple)) and len(inputs) == 3
@@ -228,7 +227,7 @@ class GcnFusedRoute:
                 and w.dtype == torch.float32 and w.dim() == 2 and int(w.shape[1]) == 1 and w.is_contiguous()
                 and idx.dtype == torch.int64 and idx.dim() == 2 and int(idx.shape[1]) == 2
                 and int(w.shape[0]) == int(idx.shape[0]) and inputs[0].nrows() == inputs[2].nrows()
-                and not needs_grad(x, w))
+                and not needs_grad(x, w, *self._weights()))
 
     @staticmethod
     def _key(node, edge_w, idx):

@@ -473,9 +473,8 @@ class PainnFusedRoute:
         self._groups, self.max_groups = {}, 4     # launch groups (call_group): k bound batches served by one launch sequence
         self.last = None
 
-    @staticmethod
-    def accepts(inputs, with_forces=False):
-        from .autograd import needs_grad
+    def accepts(self, inputs, with_forces=False):
+        from .autograd import needs_grad, route_weights_need_grad
         from .ragged import RaggedTensor
         if not (isinstance(inputs, (list, tuple)) and len(inputs) == 3
                 and all(isinstance(x, RaggedTensor) for x in inputs)):
@@ -485,7 +484,7 @@ class PainnFusedRoute:
                 and xyz.dim() == 2 and int(xyz.shape[1]) == 3 and idx.dtype == torch.int64 and idx.dim() == 2
                 and int(idx.shape[1]) == 2 and z.is_contiguous() and xyz.is_contiguous() and idx.is_contiguous()
                 and int(xyz.shape[0]) == int(z.shape[0]) and inputs[0].nrows() == inputs[2].nrows()
-                and (with_forces or not needs_grad(z, xyz)))
+                and (with_forces or not needs_grad(z, xyz)) and not route_weights_need_grad(self))
 
     def _sync_weights(self):
         # Fast path (every call): the version counters of the tensors seen at the last full check - in-place updates

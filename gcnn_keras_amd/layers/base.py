@@ -47,7 +47,14 @@ def weight_epoch():
 
 
 class Layer:
-    """Just enough of ``ks.layers.Layer``: naming, lazy build, weights, ``get_config``."""
+    """Just enough of ``ks.layers.Layer``: naming, lazy build, weights, ``get_config``.
+
+    ``weight_gradients``: the layer's call produces correct gradients for its weights (and those of its sublayers) under
+    torch autograd.  A layer without it raises ``NotImplementedError`` when it is called in grad mode while one of its
+    weights requires grad, instead of leaving that weight silently out of the tape.  Layers opt in once their weight
+    gradients are tested."""
+
+    weight_gradients = False
 
     def __setattr__(self, key, value):
         if torch.is_tensor(value):
@@ -133,7 +140,8 @@ class Layer:
             a = np.asarray(a, dtype=np.float32)
             if tuple(a.shape) != tuple(t.shape):
                 raise ValueError("Shape mismatch for %s: %s vs %s" % (n, tuple(a.shape), tuple(t.shape)))
-            t.copy_(torch.from_numpy(a))
+            with torch.no_grad():
+                t.copy_(torch.from_numpy(a))
 
     # -- call protocol -----------------------------------------------------------------------------------------
     @staticmethod
@@ -159,7 +167,16 @@ class Layer:
 
     def __call__(self, inputs, **kwargs):
         self.ensure_built(self._shape_of(inputs))
+        if not self.weight_gradients and torch.is_grad_enabled():
+            self._check_no_trainable_weights()
         return self.call(inputs, **kwargs)
+
+    def _check_no_trainable_weights(self):
+        for n, t in self.weights:
+            if t is not None and t.requires_grad:
+                raise NotImplementedError("%s (%s): weight gradients are not implemented for this layer (weight %s "
+                                          "requires grad); call it under torch.no_grad() or with frozen weights"
+                                          % (self.name, type(self).__name__, n))
 
     def get_config(self):
         return {"name": self.name, "trainable": self.trainable, "dtype": self.dtype}

@@ -7,6 +7,8 @@ from .base import GraphBaseLayer
 
 
 class ChangeTensorType(GraphBaseLayer):
+    weight_gradients = True   # layers/base.py: no weight of this layer is left off the tape
+
 
     def __init__(self, input_tensor_type: str = "RaggedTensor", output_tensor_type: str = "RaggedTensor",
                  partition_type: str = "row_length", shape=None, default_value=None, boolean_mask: bool = False,

@@ -10,6 +10,8 @@ from ..pooling import PoolingWeightedLocalEdges
 class GCN(GraphBaseLayer):
     r""":math:`\sigma(A_s (XW + b))` with the pre-scaled adjacency given as edge weights ``(batch, [M], 1)``."""
 
+    weight_gradients = True   # layers/base.py: no weight of this layer is left off the tape
+
     def __init__(self, units, pooling_method="sum", normalize_by_weights=False, activation="kgcnn>leaky_relu",
                  use_bias=True, kernel_regularizer=None, bias_regularizer=None, activity_regularizer=None,
                  kernel_constraint=None, bias_constraint=None, kernel_initializer="glorot_uniform",

@@ -40,6 +40,8 @@ class SchNetCFconv(GraphBaseLayer):
     r"""``out_i = pool_{e: recv(e)=i} x_{send(e)} * Dense(units)(Dense(units, act)(edge_e))``
     (reference kgcnn/layers/conv/schnet_conv.py:9-89)."""
 
+    weight_gradients = True   # layers/base.py: no weight of this layer is left off the tape
+
     def __init__(self, units, cfconv_pool="segment_sum", use_bias=True, activation="kgcnn>shifted_softplus",
                  kernel_regularizer=None, bias_regularizer=None, activity_regularizer=None, kernel_constraint=None,
                  bias_constraint=None, kernel_initializer="glorot_uniform", bias_initializer="zeros", **kwargs):
@@ -65,17 +67,44 @@ class SchNetCFconv(GraphBaseLayer):
         return (self.units == 128 and self.cfconv_pool in _SUM_NAMES and self.lay_dense1.activation in _SSP_NAMES
                 and node.values.dim() == 2 and int(node.values.shape[1]) == 128 and edge.values.dim() == 2
                 and int(edge.values.shape[1]) <= 32 and self.lay_sum.pooling_index == 0
-                and self.lay_sum.has_unconnected and not needs_grad(node.values, edge.values))
+                and self.lay_sum.has_unconnected and not needs_grad(node.values, edge.values, *self._filter_weights()))
+
+    def _filter_weights(self):
+        return (self.lay_dense1.kernel, self.lay_dense1.bias, self.lay_dense2.kernel, self.lay_dense2.bias)
 
     def _packed_weights(self, basis):
-        tensors = (self.lay_dense1.kernel, self.lay_dense1.bias, self.lay_dense2.kernel, self.lay_dense2.bias)
-        key = tuple((t.data_ptr(), t._version) if t is not None else None for t in tensors)
+        tensors = self._filter_weights()
+        key = (basis,) + tuple((t.data_ptr(), t._version) if t is not None else None for t in tensors)
         if self._packed is None or key != self._packed_key:
-            buf = torch.empty(_ffi.lib().mp_cfconv_packed_floats(), dtype=torch.float32, device=tensors[0].device)
+            # same tensors and basis, new values (an optimizer step, set_weights): re-fill the image in place, so that a
+            # HIP graph captured around this layer reads the new weights; other tensors: a new image
+            same = self._packed_key is not None and self._packed is not None and self._addresses(self._packed_key) == \
+                self._addresses(key)
+            buf = self._packed if same else torch.empty(_ffi.lib().mp_cfconv_packed_floats(), dtype=torch.float32,
+                                                        device=tensors[0].device)
             _ffi.call("mp_cfconv_pack_f32", _ffi.ptr(tensors[0]), _ffi.ptr(tensors[1]), basis, _ffi.ptr(tensors[2]),
                       _ffi.ptr(tensors[3]), _ffi.ptr(buf), _ffi.stream())
             self._packed, self._packed_key = buf, key
         return self._packed
+
+    @staticmethod
+    def _addresses(key):
+        return (key[0],) + tuple(k[0] if k is not None else None for k in key[1:])
+
+    def refresh_packed(self):
+        """Called before a captured graph that contains the fused cfconv is replayed (``engine.GraphedModel``): the graph
+        reads ``self._packed``, which only a call of this layer refreshes.  Re-fills the image in place after in-place
+        weight updates; raises if the weight tensors were replaced (the graph holds the old image)."""
+        if self._packed is None:
+            return
+        basis = self._packed_key[0]
+        key = (basis,) + tuple((t.data_ptr(), t._version) if t is not None else None for t in self._filter_weights())
+        if key == self._packed_key:
+            return
+        if self._addresses(key) != self._addresses(self._packed_key):
+            raise _ffi.EngineError("%s: filter weight tensors were replaced after a graph capture; capture again"
+                                   % self.name)
+        self._packed_weights(basis)
 
     def _call_fused(self, node, edge, indexlist):
         plan = indexlist.index_plan(node)
@@ -117,6 +146,8 @@ class SchNetInteraction(GraphBaseLayer):
     r"""``n + Dense(lin)(Dense(act)(cfconv(Dense_nobias(n), edges, idx)))``
     (reference kgcnn/layers/conv/schnet_conv.py:93-174)."""
 
+    weight_gradients = True   # layers/base.py: no weight of this layer is left off the tape
+
     def __init__(self, units=128, cfconv_pool="sum", use_bias=True, activation="kgcnn>shifted_softplus",
                  kernel_regularizer=None, bias_regularizer=None, activity_regularizer=None, kernel_constraint=None,
                  bias_constraint=None, kernel_initializer="glorot_uniform", bias_initializer="zeros", **kwargs):
@@ -146,7 +177,8 @@ class SchNetInteraction(GraphBaseLayer):
         nv, uv = node.values, update.values
         if (self.units == 128 and self.lay_dense2.activation in _SSP_NAMES and nv.dim() == 2 and uv.dim() == 2
                 and tuple(nv.shape) == tuple(uv.shape) and int(nv.shape[1]) == 128 and nv.dtype == torch.float32
-                and not needs_grad(nv, uv)):
+                and not needs_grad(nv, uv, self.lay_dense2.kernel, self.lay_dense2.bias, self.lay_dense3.kernel,
+                                   self.lay_dense3.bias)):
             # node side in ONE kernel (csrc/mp_schnet_node.hip, 16-node tiles, both 128x128 GEMMs on FP32 MFMA with the
             # hidden tile handed over in LDS, residual add in the epilogue) instead of Dense, Dense, LazyAdd
             _ffi.require_device(nv, uv)

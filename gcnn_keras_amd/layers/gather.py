@@ -40,6 +40,8 @@ class GatherEmbedding(GraphBaseLayer):
     ``axis == 1``, concat / split axis ``None`` or 2) is one gather kernel; other concat / split axes take the general
     route of gather.py:121-138 (same gather + strided re-arrangement); only ``axis != 1`` (ragged rank 2 in TF) raises."""
 
+    weight_gradients = True   # layers/base.py: no weight of this layer is left off the tape
+
     def __init__(self, axis: int = 1, concat_axis: int = 2, split_axis: int = None, split_indices: list = None,
                  concat_indices: list = None, node_indexing: str = "sample", **kwargs):
         super().__init__(node_indexing=node_indexing, **kwargs)
@@ -119,6 +121,8 @@ GatherNodes = GatherEmbedding
 class GatherEmbeddingSelection(GraphBaseLayer):
     r"""Gather embeddings for the given index columns; always returns a list (kgcnn/layers/gather.py:153-245)."""
 
+    weight_gradients = True   # layers/base.py: no weight of this layer is left off the tape
+
     def __init__(self, selection_index, axis: int = 1, axis_indices: int = 2, **kwargs):
         super().__init__(**kwargs)
         self.axis = axis
@@ -167,6 +171,8 @@ class GatherNodesOutgoing(GatherEmbeddingSelection):
 
 class GatherState(GraphBaseLayer):
     r"""Repeat a per-graph state for every node / edge of its graph (kgcnn/layers/gather.py:323-375)."""
+
+    weight_gradients = True   # layers/base.py: no weight of this layer is left off the tape
 
     def call(self, inputs, **kwargs):
         env, target = inputs[0], inputs[1]

@@ -12,6 +12,8 @@ from .modules import LazyMultiply, LazySubtract
 class NodePosition(GraphBaseLayer):
     r"""Node positions for the two ends of every edge = ``GatherNodesSelection([0, 1])`` (kgcnn/layers/geom.py:14-73)."""
 
+    weight_gradients = True   # layers/base.py: no weight of this layer is left off the tape
+
     def __init__(self, selection_index: list = None, **kwargs):
         super().__init__(**kwargs)
         if selection_index is None:
@@ -42,6 +44,8 @@ def _rdc(values, axis_values):
 
 class EuclideanNorm(GraphBaseLayer):
     r"""``sqrt(relu(sum_axis x^2))`` with optional eps / inversion (kgcnn/layers/geom.py:127-214)."""
+
+    weight_gradients = True   # layers/base.py: no weight of this layer is left off the tape
 
     def __init__(self, axis: int = -1, keepdims: bool = False, invert_norm: bool = False, add_eps: bool = False,
                  no_nan: bool = True, square_norm: bool = False, **kwargs):
@@ -89,6 +93,8 @@ class EuclideanNorm(GraphBaseLayer):
 class ScalarProduct(GraphBaseLayer):
     r"""``sum_axis a*b`` (kgcnn/layers/geom.py:218-281)."""
 
+    weight_gradients = True   # layers/base.py: no weight of this layer is left off the tape
+
     def __init__(self, axis=-1, **kwargs):
         super().__init__(**kwargs)
         self.axis = axis
@@ -125,6 +131,8 @@ class ScalarProduct(GraphBaseLayer):
 class NodeDistanceEuclidean(GraphBaseLayer):
     r"""``||x_1 - x_2||`` with kept last axis, shape ``(batch, [M], 1)`` (kgcnn/layers/geom.py:285-327)."""
 
+    weight_gradients = True   # layers/base.py: no weight of this layer is left off the tape
+
     def __init__(self, add_eps: bool = False, no_nan: bool = True, **kwargs):
         super().__init__(**kwargs)
         self.layer_subtract = LazySubtract()
@@ -143,6 +151,8 @@ class NodeDistanceEuclidean(GraphBaseLayer):
 
 class EdgeDirectionNormalized(GraphBaseLayer):
     r"""``(r_i - r_j) / ||r_i - r_j||`` with ``divide_no_nan`` (kgcnn/layers/geom.py:331-378)."""
+
+    weight_gradients = True   # layers/base.py: no weight of this layer is left off the tape
 
     def __init__(self, add_eps: bool = False, no_nan: bool = True, **kwargs):
         super().__init__(**kwargs)
@@ -166,6 +176,8 @@ class EdgeDirectionNormalized(GraphBaseLayer):
 class GaussBasisLayer(GraphBaseLayer):
     r"""Gaussian radial basis ``exp(-gamma (d - offset - mu_k)^2)``, ``mu_k = k / bins * distance``,
     ``gamma = 1 / (2 sigma^2)`` (kgcnn/layers/geom.py:514-592)."""
+
+    weight_gradients = True   # layers/base.py: no weight of this layer is left off the tape
 
     def __init__(self, bins: int = 20, distance: float = 4.0, sigma: float = 0.4, offset: float = 0.0, **kwargs):
         super().__init__(**kwargs)
@@ -241,6 +253,8 @@ class BesselBasisLayer(GraphBaseLayer):
 
 class CosCutOffEnvelope(GraphBaseLayer):
     r"""``0.5 (cos(pi d / R_c) + 1)`` on clipped distances; ``cutoff=None`` means 1e8 (kgcnn/layers/geom.py:809-856)."""
+
+    weight_gradients = True   # layers/base.py: no weight of this layer is left off the tape
 
     def __init__(self, cutoff, **kwargs):
         super().__init__(**kwargs)

@@ -15,6 +15,8 @@ class MLPBase(GraphBaseLayer):
     r"""Argument broadcasting of kgcnn/layers/mlp.py:12-242: every per-layer argument may be a single value or a
     list matching ``units``."""
 
+    weight_gradients = True   # layers/base.py: no weight of this layer is left off the tape
+
     _KEYS = ["activation", "activity_regularizer", "units", "use_bias", "kernel_regularizer", "bias_regularizer",
              "kernel_initializer", "bias_initializer", "kernel_constraint", "bias_constraint",
              "use_dropout", "use_normalization", "normalization_technique", "rate", "noise_shape", "seed",

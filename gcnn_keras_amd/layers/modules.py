@@ -45,7 +45,7 @@ def dense_values(x, kernel, bias, activation="linear", alpha=0.05):
         raise ValueError("Dense kernel expects last dimension %d, got %d" % (int(kernel.shape[0]), int(x.shape[-1])))
     name = _activation_name(activation)
     code = 0 if name == "softmax" else _ffi.activation_code(name)
-    if needs_grad(x):
+    if needs_grad(x, kernel, bias):
         out = DenseFn.apply(x, kernel, bias, code, float(alpha))
     else:
         out = _dense_raw(x, kernel, bias, code, alpha)
@@ -55,6 +55,8 @@ def dense_values(x, kernel, bias, activation="linear", alpha=0.05):
 class DenseEmbedding(GraphBaseLayer):
     r"""Dense layer on the flat values of a ragged tensor, :math:`\sigma(xW + b)` (kgcnn/layers/modules.py:15-90).
     Kernel layout ``(in, units)`` and initialisers as in Keras (``glorot_uniform`` / ``zeros``)."""
+
+    weight_gradients = True   # layers/base.py: no weight of this layer is left off the tape
 
     def __init__(self, units: int, activation=None, use_bias: bool = True, kernel_initializer="glorot_uniform",
                  bias_initializer="zeros", kernel_regularizer=None, bias_regularizer=None, activity_regularizer=None,
@@ -100,6 +102,8 @@ Dense = DenseEmbedding
 class ActivationEmbedding(GraphBaseLayer):
     """Activation on the values of a ragged tensor (kgcnn/layers/modules.py:94-138)."""
 
+    weight_gradients = True   # layers/base.py: no weight of this layer is left off the tape
+
     def __init__(self, activation, activity_regularizer=None, **kwargs):
         super().__init__(**kwargs)
         self.activation = _activation_name(activation)
@@ -126,6 +130,8 @@ Activation = ActivationEmbedding
 
 class DropoutEmbedding(GraphBaseLayer):
     """Dropout (kgcnn/layers/modules.py:142-183): identity outside training - the engine is forward / inference only."""
+
+    weight_gradients = True   # layers/base.py: no weight of this layer is left off the tape
 
     def __init__(self, rate, noise_shape=None, seed=None, **kwargs):
         super().__init__(**kwargs)
@@ -210,12 +216,16 @@ def _reduce_list(op, values):
 class LazyAdd(GraphBaseLayer):
     r"""Sum of a list of (ragged) tensors on their values (kgcnn/layers/modules.py:187-212)."""
 
+    weight_gradients = True   # layers/base.py: no weight of this layer is left off the tape
+
     def call(self, inputs, **kwargs):
         return self.map_values(lambda vals: _reduce_list(_ffi.MP_ADD, vals), inputs, **kwargs)
 
 
 class LazySubtract(GraphBaseLayer):
     r"""``inputs[0] - inputs[1]`` on values (kgcnn/layers/modules.py:216-241)."""
+
+    weight_gradients = True   # layers/base.py: no weight of this layer is left off the tape
 
     def call(self, inputs, **kwargs):
         if len(inputs) != 2:
@@ -225,6 +235,8 @@ class LazySubtract(GraphBaseLayer):
 
 class LazyAverage(GraphBaseLayer):
     r"""Element-wise average of a list of tensors (kgcnn/layers/modules.py:245-271)."""
+
+    weight_gradients = True   # layers/base.py: no weight of this layer is left off the tape
 
     def call(self, inputs, **kwargs):
         def avg(vals):
@@ -236,6 +248,8 @@ class LazyAverage(GraphBaseLayer):
 
 class LazyMultiply(GraphBaseLayer):
     r"""Element-wise product of a list of tensors, broadcasting unit axes (kgcnn/layers/modules.py:275-301)."""
+
+    weight_gradients = True   # layers/base.py: no weight of this layer is left off the tape
 
     def call(self, inputs, **kwargs):
         return self.map_values(lambda vals: _reduce_list(_ffi.MP_MUL, vals), inputs, **kwargs)
@@ -295,6 +309,8 @@ class LazyConcatenate(GraphBaseLayer):
     r"""Concatenate a list of tensors along ``axis`` (kgcnn/layers/modules.py:305-364); the engine supports the last
     axis, which is what every hot-path model uses."""
 
+    weight_gradients = True   # layers/base.py: no weight of this layer is left off the tape
+
     def __init__(self, axis=-1, **kwargs):
         super().__init__(**kwargs)
         self.axis = axis
@@ -324,6 +340,8 @@ class LazyConcatenate(GraphBaseLayer):
 class ExpandDims(GraphBaseLayer):
     r"""``tf.expand_dims`` on the values (kgcnn/layers/modules.py:368-416); a pure view."""
 
+    weight_gradients = True   # layers/base.py: no weight of this layer is left off the tape
+
     def __init__(self, axis: int = -1, **kwargs):
         super().__init__(**kwargs)
         self.axis = axis
@@ -346,6 +364,8 @@ class ExpandDims(GraphBaseLayer):
 class ZerosLike(GraphBaseLayer):
     r"""Zero tensor with the partition of the input (kgcnn/layers/modules.py:420-446)."""
 
+    weight_gradients = True   # layers/base.py: no weight of this layer is left off the tape
+
     def call(self, inputs, **kwargs):
         return self.map_values(torch.zeros_like, inputs)
 
@@ -353,6 +373,8 @@ class ZerosLike(GraphBaseLayer):
 class OptionalInputEmbedding(GraphBaseLayer):
     r"""Optional ``Embedding`` of integer-valued node numbers (kgcnn/layers/modules.py:450-534); table
     ``(input_dim, output_dim)``, ``uniform`` init; float inputs are cast to int32 like Keras does."""
+
+    weight_gradients = True   # layers/base.py: no weight of this layer is left off the tape
 
     def __init__(self, input_dim, output_dim, use_embedding=False, embeddings_initializer="uniform",
                  embeddings_regularizer=None, activity_regularizer=None, embeddings_constraint=None, mask_zero=False,
@@ -381,6 +403,10 @@ class OptionalInputEmbedding(GraphBaseLayer):
         _ffi.require_device(vals)
         numbers = vals.to(torch.float32).contiguous()
         n = numbers.numel()
+        from ..autograd import Embedding as EmbeddingFn, needs_grad
+        if needs_grad(self.embeddings):
+            out = EmbeddingFn.apply(numbers, self.embeddings)
+            return inputs.with_values(out) if isinstance(inputs, RaggedTensor) else out
         out = torch.empty(tuple(numbers.shape) + (self.output_dim,), dtype=torch.float32, device=vals.device)
         _ffi.call("mp_embedding_f32", _ffi.ptr(self.embeddings), self.input_dim, self.output_dim, _ffi.ptr(numbers), n,
                   _ffi.ptr(out), None, _ffi.stream())

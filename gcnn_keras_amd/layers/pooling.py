@@ -30,6 +30,8 @@ class PoolingLocalEdges(GraphBaseLayer):
     r"""Aggregate edge embeddings at the receiving node ``i = idx[:, pooling_index]``
     (kgcnn/layers/pooling.py:11-88).  **Default ``pooling_method`` is "mean"** like the reference."""
 
+    weight_gradients = True   # layers/base.py: no weight of this layer is left off the tape
+
     def __init__(self, pooling_method="mean", pooling_index=0, **kwargs):
         super().__init__(**kwargs)
         self.pooling_method = pooling_method
@@ -53,6 +55,8 @@ PoolingLocalMessages = PoolingLocalEdges
 class PoolingWeightedLocalEdges(GraphBaseLayer):
     r"""Weighted aggregation (kgcnn/layers/pooling.py:92-182): ``edges * weights`` is formed BEFORE the reduce for
     every method; ``normalize_by_weights`` divides by the segment sum of weights with ``divide_no_nan``."""
+
+    weight_gradients = True   # layers/base.py: no weight of this layer is left off the tape
 
     def __init__(self, pooling_method="mean", normalize_by_weights=False, pooling_index=0, **kwargs):
         super().__init__(**kwargs)
@@ -111,6 +115,8 @@ def _pool_graph(x, op, weights=None):
 class PoolingEmbedding(GraphBaseLayer):
     """Pool all nodes (or edges) of each graph to a graph embedding tensor (kgcnn/layers/pooling.py:186-229)."""
 
+    weight_gradients = True   # layers/base.py: no weight of this layer is left off the tape
+
     def __init__(self, pooling_method="mean", **kwargs):
         super().__init__(**kwargs)
         self.pooling_method = pooling_method
@@ -131,6 +137,8 @@ PoolingGlobalEdges = PoolingEmbedding
 
 class PoolingWeightedEmbedding(GraphBaseLayer):
     """Weighted per-graph pooling (kgcnn/layers/pooling.py:233-284)."""
+
+    weight_gradients = True   # layers/base.py: no weight of this layer is left off the tape
 
     def __init__(self, pooling_method="mean", **kwargs):
         super().__init__(**kwargs)

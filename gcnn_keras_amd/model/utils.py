@@ -66,7 +66,13 @@ class Model:
     distinct input set (identified by the storage of its tensors), how often it was called: the first call runs eagerly
     (building and caching the index plans on the ragged inputs), the second captures the same call sequence into ONE HIP
     graph (``engine.GraphedModel``), later calls replay it and return a fresh copy of the output.  Calls that ask for
-    gradients, pass keyword arguments, or whose capture fails (a layer that needs a host read per call) stay eager.
+    gradients (inputs or weights that require grad, in grad mode), pass keyword arguments, or whose capture fails (a
+    layer that needs a host read per call) stay eager.
+
+    Training (the Keras ``compile`` / ``fit`` pair, kgcnn/training/train_qm.py:159-166): ``compile(optimizer, loss)`` then
+    ``train_on_batch(x, y, sample_weight)`` - one step of zero grads, layer-path forward, loss, backward (the engine's
+    reverse rules, weight gradients included) and ``optimizer.step()``.  The weights require grad only inside the step, so
+    between steps every call takes the same (fused / graph-replayed) route as an untrained model.
     """
 
     def __init__(self, name, forward, layers, config=None, auto_graph=False, max_graphs=4):
@@ -78,9 +84,12 @@ class Model:
         self.max_graphs = int(max_graphs)
         self._graphs = {}      # input identity -> [calls, GraphedModel | None | False]
         self.last_route = None  # "eager" | "graph"
+        self.optimizer = None
+        self.loss = None
+        self._loss_fn = None
 
     def __call__(self, inputs, **kwargs):
-        if self.auto_graph and not kwargs:
+        if self.auto_graph and not kwargs and not self._weights_need_grad():
             key = self._graph_key(inputs)
             if key is not None:
                 return self._call_graphed(key, inputs)
@@ -118,7 +127,7 @@ class Model:
         if entry[1] is None:
             from ..engine import GraphedModel
             try:
-                entry[1] = GraphedModel(self._forward, inputs, grad=False)
+                entry[1] = GraphedModel(self._forward, inputs, grad=False, layers=self.layers)
             except Exception:   # e.g. a layer that reads a size back per call cannot be captured: stay eager
                 import torch
                 torch.cuda.synchronize()
@@ -136,6 +145,16 @@ class Model:
     def release_graphs(self):
         self._graphs.clear()
 
+    def _weights_need_grad(self):
+        import torch
+        if not torch.is_grad_enabled():
+            return False
+        for lay in self.layers:
+            for _, t in lay.weights:
+                if t is not None and t.requires_grad:
+                    return True
+        return False
+
     predict = __call__
 
     @property
@@ -145,8 +164,62 @@ class Model:
             out.extend((lay.name + "/" + n, t) for n, t in lay.weights)
         return out
 
+    @property
+    def trainable_weights(self):
+        """The weight tensors in ``weights`` order (the Keras name)."""
+        return [t for _, t in self.weights]
+
+    def requires_grad_(self, flag=True):
+        """Switch ``requires_grad`` of every weight (for a hand-written torch training loop).  While on, calls in grad
+        mode take the layer path, which records the weights on the tape."""
+        for t in self.trainable_weights:
+            t.requires_grad_(bool(flag))
+        return self
+
     def get_weights(self):
         return [t.detach().cpu().numpy() for _, t in self.weights]
+
+    # -- training --------------------------------------------------------------------------------------------------------
+    def compile(self, optimizer="adam", loss="mean_absolute_error"):
+        """``optimizer``: a ``torch.optim.Optimizer`` over ``trainable_weights``, or ``"adam"`` / ``"sgd"`` with Keras'
+        defaults (Adam lr 1e-3, betas (0.9, 0.999), epsilon 1e-7; SGD lr 0.01).  ``loss``: ``"mean_absolute_error"``,
+        ``"mean_squared_error"`` or ``"categorical_crossentropy"`` (Keras semantics, reduction sum over batch size)."""
+        import torch
+        from .losses import get_loss
+        loss_fn = get_loss(loss)
+        if isinstance(optimizer, str):
+            name = optimizer.lower()
+            if name == "adam":
+                optimizer = torch.optim.Adam(self.trainable_weights, lr=1e-3, betas=(0.9, 0.999), eps=1e-7)
+            elif name == "sgd":
+                optimizer = torch.optim.SGD(self.trainable_weights, lr=0.01)
+            else:
+                raise ValueError("Unknown optimizer %r (use 'adam', 'sgd' or a torch.optim.Optimizer)" % (optimizer,))
+        elif not isinstance(optimizer, torch.optim.Optimizer):
+            raise ValueError("optimizer must be 'adam', 'sgd' or a torch.optim.Optimizer, got %r" % (optimizer,))
+        self.optimizer, self.loss, self._loss_fn = optimizer, loss, loss_fn
+        return self
+
+    def train_on_batch(self, x, y, sample_weight=None):
+        """One optimizer step on ``(x, y)``; returns the loss before the step (a Python float)."""
+        import torch
+        if self.optimizer is None:
+            raise RuntimeError("Model %s: call compile(optimizer, loss) before train_on_batch" % self.name)
+        weights = self.trainable_weights
+        saved = [t.requires_grad for t in weights]
+        try:
+            for t in weights:
+                t.requires_grad_(True)
+            self.optimizer.zero_grad(set_to_none=True)
+            with torch.enable_grad():
+                pred = self._forward(x)
+                loss = self._loss_fn(pred, y, sample_weight)
+                loss.backward()
+            self.optimizer.step()
+        finally:
+            for t, flag in zip(weights, saved):
+                t.requires_grad_(flag)
+        return float(loss.detach())
 
     def set_weights(self, arrays):
         ws = self.weights
@@ -158,4 +231,5 @@ class Model:
             a = np.asarray(a, dtype=np.float32)
             if tuple(a.shape) != tuple(t.shape):
                 raise ValueError("Shape mismatch for %s: %s vs %s" % (n, tuple(a.shape), tuple(t.shape)))
-            t.copy_(torch.from_numpy(a))
+            with torch.no_grad():
+                t.copy_(torch.from_numpy(a))

@@ -26,6 +26,9 @@ def shifted_softplus(x):
 def softmax(x):
     """Keras ``softmax`` on the last axis."""
     _ffi.require_device(x)
+    from ..autograd import Softmax, needs_grad
+    if needs_grad(x):
+        return Softmax.apply(x)
     xc = x.contiguous()
     c = int(xc.shape[-1])
     out = torch.empty_like(xc)
