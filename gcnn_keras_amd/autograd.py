@@ -6,10 +6,34 @@ ids, Dense-backward = Dense with the transposed kernel, plus the elementwise der
 Weight gradients (training, ``Model.train_on_batch``) come from csrc/mp_wgrad.hip: dW = x^T g and db = sum_r g for
 Dense, the embedding table gradient, and the reverse of the row softmax.  Each is produced only when
 ``ctx.needs_input_grad`` asks for it.
+
+Second order (a loss on forces, ``EnergyForceModel.train_on_batch``): a backward that runs in grad mode
+(``torch.autograd.grad(E, x, create_graph=True)``) records itself on the tape.  The rules of the SchNet force path do so
+through the ``*Adjoint`` functions below, whose forward is the first-order computation and whose backward is its reverse:
+a gather for a segment sum and back, the Dense GEMMs and wgrad, and the elementwise second derivatives of
+csrc/mp_backward2.hip.  In no-grad mode (every inference tape, every loss on the outputs alone) each rule runs the same
+kernels as before.  The other rules are ``once_differentiable``: differentiating them twice raises.
 """
+import contextlib
+
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _ffi
+
+_input_grads_only = [False]
+
+
+@contextlib.contextmanager
+def input_grads_only():
+    """Inside, the rules skip the gradients of their weights (``EnergyForceModel``'s force pass asks for dE/dx alone,
+    while torch still marks every Dense kernel as needing a gradient)."""
+    prev = _input_grads_only[0]
+    _input_grads_only[0] = True
+    try:
+        yield
+    finally:
+        _input_grads_only[0] = prev
 
 
 def needs_grad(*tensors):
@@ -50,19 +74,38 @@ class GatherRows(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        from .ops.segment import _segment_reduce_raw
-        plan = ctx.plan
-        total = None
-        for j, col in enumerate(ctx.colsel):
-            ptr, perm, _ = plan.csr(col)
-            gj = g[:, j].contiguous()
-            part = _segment_reduce_raw(_ffi.MP_SUM, gj, ptr, perm, plan.N, None, False)
-            if total is None:
-                total = part
-            else:
-                from .layers.modules import _binary_raw
-                total = _binary_raw(_ffi.MP_ADD, total, part)
-        return total.view(ctx.shape), None, None
+        if torch.is_grad_enabled():
+            return GatherRowsAdjoint.apply(g, ctx.plan, ctx.colsel, ctx.shape), None, None
+        return _gather_rows_adjoint(g, ctx.plan, ctx.colsel, ctx.shape), None, None
+
+
+def _gather_rows_adjoint(g, plan, colsel, shape):
+    """Reverse of GatherRows: per gathered column, the CSR segment sum of its slice of ``g``."""
+    from .ops.segment import _segment_reduce_raw
+    total = None
+    for j, col in enumerate(colsel):
+        ptr, perm, _ = plan.csr(col)
+        gj = g[:, j].contiguous()
+        part = _segment_reduce_raw(_ffi.MP_SUM, gj, ptr, perm, plan.N, None, False)
+        if total is None:
+            total = part
+        else:
+            from .layers.modules import _binary_raw
+            total = _binary_raw(_ffi.MP_ADD, total, part)
+    return total.view(shape)
+
+
+class GatherRowsAdjoint(torch.autograd.Function):
+    """GatherRows' backward as a differentiable op of ``g``; its own backward is the gather again."""
+
+    @staticmethod
+    def forward(ctx, g, plan, colsel, shape):
+        ctx.plan, ctx.colsel = plan, colsel
+        return _gather_rows_adjoint(g, plan, colsel, shape)
+
+    @staticmethod
+    def backward(ctx, h):
+        return GatherRows.apply(h.contiguous(), ctx.plan, ctx.colsel), None, None, None
 
 
 class SegmentSum(torch.autograd.Function):
@@ -73,26 +116,49 @@ class SegmentSum(torch.autograd.Function):
         from .ops.segment import _segment_reduce_raw
         if op not in (_ffi.MP_SUM, _ffi.MP_MEAN):
             raise NotImplementedError("gradients are implemented for sum / mean pooling")
-        ctx.op, ctx.ptr, ctx.n_out, ctx.weight, ctx.seg_ids = op, ptr, n_out, weight, seg_ids
+        ctx.op, ctx.ptr, ctx.perm, ctx.n_out, ctx.weight, ctx.seg_ids = op, ptr, perm, n_out, weight, seg_ids
         ctx.shape = tuple(data.shape)
         return _segment_reduce_raw(op, data, ptr, perm, n_out, weight, False)
 
     @staticmethod
     def backward(ctx, g):
-        gc = g.contiguous()
-        rows, elems = _rows_elems(gc)
-        m = int(ctx.seg_ids.numel())
-        if ctx.op == _ffi.MP_MEAN:
-            cnt = (ctx.ptr[1:ctx.n_out + 1] - ctx.ptr[:ctx.n_out]).to(torch.float32).clamp(min=1.0)
-            from .layers.modules import _binary_raw
-            gc = _binary_raw(_ffi.MP_MUL, gc.view(rows, elems), (1.0 / cnt).view(rows, 1)).view(gc.shape)
-        out = torch.empty((m,) + tuple(gc.shape[1:]), dtype=torch.float32, device=gc.device)
-        _ffi.call("mp_gather_rows_f32", _ffi.ptr(gc), rows, elems, _ffi.ptr(ctx.seg_ids.contiguous()), m, 1,
-                  _ffi.int32_array([0]), _ffi.ptr(out), _ffi.stream())
-        if ctx.weight is not None:
-            from .layers.modules import _binary_raw
-            out = _binary_raw(_ffi.MP_MUL, out.view(m, elems), ctx.weight.contiguous().view(m, 1)).view(out.shape)
+        if torch.is_grad_enabled():
+            out = SegmentSumAdjoint.apply(g, ctx.op, ctx.ptr, ctx.perm, ctx.n_out, ctx.weight, ctx.seg_ids)
+        else:
+            out = _segment_sum_adjoint(g, ctx.op, ctx.ptr, ctx.n_out, ctx.weight, ctx.seg_ids)
         return out, None, None, None, None, None, None
+
+
+def _segment_sum_adjoint(g, op, ptr, n_out, weight, seg_ids):
+    """Reverse of SegmentSum: ``g`` gathered by the segment id of every row (divided by the count for the mean, times
+    the row weight)."""
+    gc = g.contiguous()
+    rows, elems = _rows_elems(gc)
+    m = int(seg_ids.numel())
+    if op == _ffi.MP_MEAN:
+        cnt = (ptr[1:n_out + 1] - ptr[:n_out]).to(torch.float32).clamp(min=1.0)
+        from .layers.modules import _binary_raw
+        gc = _binary_raw(_ffi.MP_MUL, gc.view(rows, elems), (1.0 / cnt).view(rows, 1)).view(gc.shape)
+    out = torch.empty((m,) + tuple(gc.shape[1:]), dtype=torch.float32, device=gc.device)
+    _ffi.call("mp_gather_rows_f32", _ffi.ptr(gc), rows, elems, _ffi.ptr(seg_ids.contiguous()), m, 1,
+              _ffi.int32_array([0]), _ffi.ptr(out), _ffi.stream())
+    if weight is not None:
+        from .layers.modules import _binary_raw
+        out = _binary_raw(_ffi.MP_MUL, out.view(m, elems), weight.contiguous().view(m, 1)).view(out.shape)
+    return out
+
+
+class SegmentSumAdjoint(torch.autograd.Function):
+    """SegmentSum's backward (gather by segment id) as a differentiable op of ``g``; its backward is the CSR segment sum."""
+
+    @staticmethod
+    def forward(ctx, g, op, ptr, perm, n_out, weight, seg_ids):
+        ctx.args = (op, ptr, perm, n_out, weight, seg_ids)
+        return _segment_sum_adjoint(g, op, ptr, n_out, weight, seg_ids)
+
+    @staticmethod
+    def backward(ctx, h):
+        return (SegmentSum.apply(h.contiguous(), *ctx.args),) + (None,) * 6
 
 
 class PoolGraph(torch.autograd.Function):
@@ -111,16 +177,35 @@ class PoolGraph(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        gc = g.contiguous()
-        _, elems = _rows_elems(gc)
-        if ctx.op == _ffi.MP_MEAN:
-            cnt = (ctx.splits[1:] - ctx.splits[:-1]).to(torch.float32).clamp(min=1.0)
-            from .layers.modules import _binary_raw
-            gc = _binary_raw(_ffi.MP_MUL, gc.view(ctx.g, elems), (1.0 / cnt).view(ctx.g, 1)).view(gc.shape)
-        out = torch.empty((ctx.n,) + tuple(gc.shape[1:]), dtype=torch.float32, device=gc.device)
-        _ffi.call("mp_repeat_rows_f32", _ffi.ptr(gc), _ffi.ptr(ctx.splits), ctx.g, elems, ctx.n, _ffi.ptr(out),
-                  _ffi.stream())
-        return out, None, None, None
+        if torch.is_grad_enabled():
+            return PoolGraphAdjoint.apply(g, ctx.op, ctx.splits, ctx.g, ctx.n), None, None, None
+        return _pool_graph_adjoint(g, ctx.op, ctx.splits, ctx.g, ctx.n), None, None, None
+
+
+def _pool_graph_adjoint(g, op, splits, g_rows, n):
+    """Reverse of PoolGraph: every graph row repeated over its nodes (divided by the node count for the mean)."""
+    gc = g.contiguous()
+    _, elems = _rows_elems(gc)
+    if op == _ffi.MP_MEAN:
+        cnt = (splits[1:] - splits[:-1]).to(torch.float32).clamp(min=1.0)
+        from .layers.modules import _binary_raw
+        gc = _binary_raw(_ffi.MP_MUL, gc.view(g_rows, elems), (1.0 / cnt).view(g_rows, 1)).view(gc.shape)
+    out = torch.empty((n,) + tuple(gc.shape[1:]), dtype=torch.float32, device=gc.device)
+    _ffi.call("mp_repeat_rows_f32", _ffi.ptr(gc), _ffi.ptr(splits), g_rows, elems, n, _ffi.ptr(out), _ffi.stream())
+    return out
+
+
+class PoolGraphAdjoint(torch.autograd.Function):
+    """PoolGraph's backward (repeat rows) as a differentiable op of ``g``; its backward is the pooling again."""
+
+    @staticmethod
+    def forward(ctx, g, op, splits, g_rows, n):
+        ctx.args = (op, splits, g_rows)
+        return _pool_graph_adjoint(g, op, splits, g_rows, n)
+
+    @staticmethod
+    def backward(ctx, h):
+        return PoolGraph.apply(h.contiguous(), *ctx.args), None, None, None, None
 
 
 def dense_wgrad(x, g, with_bias=True):
@@ -140,14 +225,17 @@ def dense_wgrad(x, g, with_bias=True):
 
 
 class Dense(torch.autograd.Function):
-    """y = act(x W + b); backward gp = dy * act'(pre), dx = gp W^T, dW = x^T gp, db = sum_rows gp (each only when asked)."""
+    """y = act(x W + b); backward gp = dy * act'(pre), dx = gp W^T, dW = x^T gp, db = sum_rows gp (each only when asked).
+    In grad mode the backward is ``DenseAdjoint``, a differentiable op of (dy, x, W, b)."""
 
     @staticmethod
     def forward(ctx, x, kernel, bias, act_code, alpha):
         from .layers.modules import _dense_raw
         pre = _dense_raw(x, kernel, bias, 0, 0.0)
-        ctx.kernel, ctx.act, ctx.alpha = kernel, act_code, alpha
-        ctx.x = x if ctx.needs_input_grad[1] else None
+        ctx.kernel, ctx.bias, ctx.act, ctx.alpha = kernel, bias, act_code, alpha
+        # x: for dW, and for the second-order terms of a backward in grad mode (dx_bar through pre needs no x, but dW_bar
+        # and the dW rows of the adjoint do)
+        ctx.x = x if (ctx.needs_input_grad[1] or ctx.needs_input_grad[0]) else None
         if act_code == 0:
             ctx.pre = None
             return pre
@@ -158,24 +246,115 @@ class Dense(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        from .layers.modules import _dense_raw
-        gc = g.contiguous()
-        if ctx.pre is not None:
-            gp = torch.empty_like(gc)
-            _ffi.call("mp_activation_grad_f32", ctx.act, float(ctx.alpha), _ffi.ptr(ctx.pre), _ffi.ptr(gc), gc.numel(),
-                      _ffi.ptr(gp), _ffi.stream())
-            gc = gp
-        gx = gw = gb = None
-        if ctx.needs_input_grad[0]:
-            wt = ctx.kernel.t().contiguous()  # (units, in): layout change only
-            gx = _dense_raw(gc, wt, None, 0, 0.0)
-        if ctx.needs_input_grad[1]:
-            gw, gb = dense_wgrad(ctx.x, gc, with_bias=ctx.needs_input_grad[2])
-        elif ctx.needs_input_grad[2]:
-            u = int(gc.shape[-1])
-            gb = torch.empty((u,), dtype=torch.float32, device=gc.device)
-            _ffi.call("mp_sum_axis_f32", _ffi.ptr(gc), 1, gc.numel() // max(u, 1), u, 1, _ffi.ptr(gb), _ffi.stream())
+        want_x = ctx.needs_input_grad[0]
+        want_w = ctx.needs_input_grad[1] and not _input_grads_only[0]
+        want_b = ctx.needs_input_grad[2] and not _input_grads_only[0]
+        if torch.is_grad_enabled():
+            gx, gw, gb = DenseAdjoint.apply(g, ctx.x, ctx.kernel, ctx.bias, ctx.pre, ctx.act, ctx.alpha, want_x, want_w,
+                                            want_b)
+            return gx, gw, gb, None, None
+        gx, gw, gb, _ = _dense_backward(g.contiguous(), ctx.x, ctx.kernel, ctx.pre, ctx.act, ctx.alpha, want_x, want_w,
+                                        want_b)
         return gx, gw, gb, None, None
+
+
+def _sum_rows(g):
+    u = int(g.shape[-1])
+    out = torch.empty((u,), dtype=torch.float32, device=g.device)
+    _ffi.call("mp_sum_axis_f32", _ffi.ptr(g), 1, g.numel() // max(u, 1), u, 1, _ffi.ptr(out), _ffi.stream())
+    return out
+
+
+def _dense_backward(gc, x, kernel, pre, act, alpha, want_x, want_w, want_b):
+    """First-order Dense backward: (dx, dW, db, gp) with gp = dy * act'(pre)."""
+    from .layers.modules import _dense_raw
+    if pre is not None:
+        gp = torch.empty_like(gc)
+        _ffi.call("mp_activation_grad_f32", act, float(alpha), _ffi.ptr(pre), _ffi.ptr(gc), gc.numel(), _ffi.ptr(gp),
+                  _ffi.stream())
+        gc = gp
+    gx = gw = gb = None
+    if want_x:
+        wt = kernel.t().contiguous()  # (units, in): layout change only
+        gx = _dense_raw(gc, wt, None, 0, 0.0)
+    if want_w:
+        gw, gb = dense_wgrad(x, gc, with_bias=want_b)
+    elif want_b:
+        gb = _sum_rows(gc)
+    return gx, gw, gb, gc
+
+
+def _add(a, b):
+    from .layers.modules import _binary_raw
+    if a is None:
+        return b
+    if b is None:
+        return a
+    return _binary_raw(_ffi.MP_ADD, a, b)
+
+
+class DenseAdjoint(torch.autograd.Function):
+    """Dense's backward (dx, dW, db) as an op of (dy, x, W, b), for a backward in grad mode.
+
+    ``pre = x W + b`` is not on the tape (the forward kernel computed it), so the reverse carries it by hand.  With
+    upstreams hx, hW, hb on dx, dW, db: h_gp = hx W + x hW + hb (on gp = dy * act'(pre)); then csrc/mp_backward2.hip gives
+    dy_bar = h_gp act'(pre) and pre_bar = h_gp dy act''(pre), and
+    x_bar = gp hW^T + pre_bar W^T,  W_bar = hx^T gp + x^T pre_bar,  b_bar = sum_rows pre_bar."""
+
+    @staticmethod
+    def forward(ctx, g, x, kernel, bias, pre, act, alpha, want_x, want_w, want_b):
+        ctx.set_materialize_grads(False)   # an output nobody uses (dW, db in the force pass) brings no upstream
+        gc = g.contiguous()
+        gx, gw, gb, gp = _dense_backward(gc, x, kernel, pre, act, alpha, want_x, want_w, want_b)
+        ctx.g, ctx.x, ctx.kernel, ctx.pre, ctx.gp, ctx.act, ctx.alpha = gc, x, kernel, pre, gp, act, alpha
+        return gx, gw, gb
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, hx, hw, hb):
+        from .layers.modules import _binary_raw, _dense_raw
+        need_g, need_x, need_w, need_b = ctx.needs_input_grad[:4]
+        x, kernel, pre, gp = ctx.x, ctx.kernel, ctx.pre, ctx.gp
+        u = int(kernel.shape[1])
+        h_gp = None
+        if hx is not None:
+            h_gp = _dense_raw(hx.contiguous(), kernel, None, 0, 0.0)
+        if hw is not None:
+            h_gp = _add(h_gp, _dense_raw(x, hw.contiguous(), hb.contiguous() if hb is not None else None, 0, 0.0))
+        elif hb is not None:
+            rows = gp.numel() // max(u, 1)
+            zero = torch.zeros((rows, u), dtype=torch.float32, device=gp.device)
+            h_gp = _add(h_gp, _binary_raw(_ffi.MP_ADD, zero, hb.contiguous().view(1, u)).view(gp.shape))
+        if h_gp is None:
+            return (None,) * 10
+        g_bar = pre_bar = None
+        if pre is None:
+            g_bar = h_gp if need_g else None
+        else:
+            want_pre = need_x or need_w or need_b
+            if need_g:
+                g_bar = torch.empty_like(h_gp)
+            if want_pre:
+                pre_bar = torch.empty_like(h_gp)
+            _ffi.call("mp_activation_grad2_f32", ctx.act, float(ctx.alpha), _ffi.ptr(pre), _ffi.ptr(ctx.g),
+                      _ffi.ptr(h_gp), _ffi.ptr(pre_bar), _ffi.ptr(g_bar), h_gp.numel(), _ffi.stream())
+        x_bar = w_bar = b_bar = None
+        if need_x:
+            if hw is not None:
+                x_bar = _dense_raw(gp, hw.t().contiguous(), None, 0, 0.0)
+            if pre_bar is not None:
+                x_bar = _add(x_bar, _dense_raw(pre_bar, kernel.t().contiguous(), None, 0, 0.0))
+        if need_w:
+            if hx is not None:
+                w_bar, _ = dense_wgrad(hx, gp, with_bias=False)
+            if pre_bar is not None:
+                w_pre, b_bar = dense_wgrad(x, pre_bar, with_bias=need_b)
+                w_bar = _add(w_bar, w_pre)
+        if need_b and b_bar is None and pre_bar is not None:
+            b_bar = _sum_rows(pre_bar)
+        if not need_b:
+            b_bar = None
+        return g_bar, x_bar, w_bar, b_bar, None, None, None, None, None, None
 
 
 class Embedding(torch.autograd.Function):
@@ -192,6 +371,7 @@ class Embedding(torch.autograd.Function):
         return out
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
         import ctypes
         gc = g.contiguous()
@@ -218,6 +398,7 @@ class Softmax(torch.autograd.Function):
         return out
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
         gc = g.contiguous()
         c = int(gc.shape[-1])
@@ -231,18 +412,43 @@ class Activation(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, act_code, alpha):
         xc = x.contiguous()
-        ctx.x, ctx.act, ctx.alpha = xc, act_code, alpha
+        ctx.x, ctx.x_in, ctx.act, ctx.alpha = xc, x, act_code, alpha
         out = torch.empty_like(xc)
         _ffi.call("mp_activation_f32", act_code, float(alpha), _ffi.ptr(xc), xc.numel(), _ffi.ptr(out), _ffi.stream())
         return out
 
     @staticmethod
     def backward(ctx, g):
-        gc = g.contiguous()
-        out = torch.empty_like(gc)
-        _ffi.call("mp_activation_grad_f32", ctx.act, float(ctx.alpha), _ffi.ptr(ctx.x), _ffi.ptr(gc), gc.numel(),
-                  _ffi.ptr(out), _ffi.stream())
-        return out, None, None
+        if torch.is_grad_enabled():
+            return ActivationAdjoint.apply(ctx.x_in, g, ctx.act, ctx.alpha).view(ctx.x.shape), None, None
+        return _activation_grad(ctx.x, g.contiguous(), ctx.act, ctx.alpha), None, None
+
+
+def _activation_grad(xc, gc, act, alpha):
+    out = torch.empty_like(gc)
+    _ffi.call("mp_activation_grad_f32", act, float(alpha), _ffi.ptr(xc), _ffi.ptr(gc), gc.numel(), _ffi.ptr(out),
+              _ffi.stream())
+    return out
+
+
+class ActivationAdjoint(torch.autograd.Function):
+    """g * act'(x) as an op of (x, g); reverse: x_bar = h g act''(x), g_bar = h act'(x) (mp_activation_grad2_f32)."""
+
+    @staticmethod
+    def forward(ctx, x, g, act, alpha):
+        xc, gc = x.contiguous(), g.contiguous()
+        ctx.xc, ctx.gc, ctx.act, ctx.alpha = xc, gc, act, alpha
+        return _activation_grad(xc, gc, act, alpha)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, h):
+        hc = h.contiguous()
+        x_bar = torch.empty_like(hc) if ctx.needs_input_grad[0] else None
+        g_bar = torch.empty_like(hc) if ctx.needs_input_grad[1] else None
+        _ffi.call("mp_activation_grad2_f32", ctx.act, float(ctx.alpha), _ffi.ptr(ctx.xc), _ffi.ptr(ctx.gc), _ffi.ptr(hc),
+                  _ffi.ptr(x_bar), _ffi.ptr(g_bar), hc.numel(), _ffi.stream())
+        return x_bar, g_bar, None, None
 
 
 def _unbroadcast(g, shape):
@@ -289,6 +495,8 @@ class Binary(torch.autograd.Function):
         from .layers.modules import _binary_raw
         gc = g.contiguous()
         ga = gb = None
+        if torch.is_grad_enabled():
+            return _binary_backward_differentiable(ctx, gc)
         if ctx.ga:
             ga = gc if ctx.op != _ffi.MP_MUL else _binary_raw(_ffi.MP_MUL, gc, ctx.b)
             ga = _unbroadcast(ga, ctx.sa)
@@ -304,6 +512,24 @@ class Binary(torch.autograd.Function):
         return ga, gb, None
 
 
+def _binary_backward_differentiable(ctx, gc):
+    """Binary's backward on Binary itself (add / sub / mul without broadcasting), so that it is differentiable again."""
+    from .layers.modules import binary_values
+    if ctx.sa != ctx.sb:
+        raise NotImplementedError("second derivative of a broadcasting elementwise op is not implemented")
+    ga = gb = None
+    if ctx.ga:
+        ga = gc if ctx.op != _ffi.MP_MUL else binary_values(_ffi.MP_MUL, gc, ctx.b)
+    if ctx.gb:
+        if ctx.op == _ffi.MP_MUL:
+            gb = binary_values(_ffi.MP_MUL, gc, ctx.a)
+        elif ctx.op == _ffi.MP_SUB:
+            gb = binary_values(_ffi.MP_SUB, torch.zeros_like(gc), gc)
+        else:
+            gb = gc
+    return ga, gb, None
+
+
 class ConcatLast(torch.autograd.Function):
     @staticmethod
     def forward(ctx, *values):
@@ -312,6 +538,7 @@ class ConcatLast(torch.autograd.Function):
         return _concat_last_raw(list(values))
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
         gc = g.contiguous()
         total = int(gc.shape[-1])
@@ -332,6 +559,7 @@ class SplitLast(torch.autograd.Function):
         return tuple(_split_last_raw(value, num))
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, *gs):
         from .layers.modules import _concat_last_raw
         return _concat_last_raw([g.contiguous() for g in gs]), None
@@ -341,19 +569,46 @@ class EuclideanNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, r, d, c, flags, out_shape):
         xc = x.contiguous()
-        ctx.x, ctx.rdc, ctx.flags = xc, (r, d, c), flags
+        ctx.x, ctx.x_in, ctx.rdc, ctx.flags = xc, x, (r, d, c), flags
         out = torch.empty(out_shape, dtype=torch.float32, device=x.device)
         _ffi.call("mp_euclidean_norm_f32", _ffi.ptr(xc), r, d, c, flags, _ffi.ptr(out), _ffi.stream())
         return out
 
     @staticmethod
     def backward(ctx, g):
+        if torch.is_grad_enabled():
+            if ctx.flags & (1 | 8):
+                raise NotImplementedError("second derivative of the inverted / squared norm is not implemented")
+            return EuclideanNormAdjoint.apply(ctx.x_in, g, ctx.rdc, ctx.flags), None, None, None, None, None
+        return _euclidean_norm_grad(ctx.x, g.contiguous(), ctx.rdc, ctx.flags), None, None, None, None, None
+
+
+def _euclidean_norm_grad(xc, gc, rdc, flags):
+    r, d, c = rdc
+    gx = torch.empty_like(xc)
+    _ffi.call("mp_euclidean_norm_grad_f32", _ffi.ptr(xc), _ffi.ptr(gc), r, d, c, flags, _ffi.ptr(gx), _ffi.stream())
+    return gx
+
+
+class EuclideanNormAdjoint(torch.autograd.Function):
+    """gx = g x / |x| as an op of (x, g) for the plain norm; reverse on mp_euclidean_norm_grad2_f32."""
+
+    @staticmethod
+    def forward(ctx, x, g, rdc, flags):
+        xc, gc = x.contiguous(), g.contiguous()
+        ctx.xc, ctx.gc, ctx.rdc, ctx.flags = xc, gc, rdc, flags
+        return _euclidean_norm_grad(xc, gc, rdc, flags)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, h):
         r, d, c = ctx.rdc
-        gc = g.contiguous()
-        gx = torch.empty_like(ctx.x)
-        _ffi.call("mp_euclidean_norm_grad_f32", _ffi.ptr(ctx.x), _ffi.ptr(gc), r, d, c, ctx.flags, _ffi.ptr(gx),
-                  _ffi.stream())
-        return gx, None, None, None, None, None
+        hc = h.contiguous()
+        x_bar = torch.empty_like(ctx.xc) if ctx.needs_input_grad[0] else None
+        g_bar = torch.empty_like(ctx.gc) if ctx.needs_input_grad[1] else None
+        _ffi.call("mp_euclidean_norm_grad2_f32", _ffi.ptr(ctx.xc), _ffi.ptr(ctx.gc), _ffi.ptr(hc), r, d, c, ctx.flags,
+                  _ffi.ptr(x_bar), _ffi.ptr(g_bar), _ffi.stream())
+        return x_bar, g_bar, None, None
 
 
 class ScalarProduct(torch.autograd.Function):
@@ -374,6 +629,7 @@ class ScalarProduct(torch.autograd.Function):
         return out
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
         from .layers.modules import _binary_raw
         ge = g.contiguous().unsqueeze(ctx.axis)
@@ -391,6 +647,7 @@ class BesselBasis(torch.autograd.Function):
         return out
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
         num_radial, cutoff, exponent = ctx.args
         gd = torch.empty_like(ctx.d)
@@ -403,7 +660,7 @@ class GaussBasis(torch.autograd.Function):
     @staticmethod
     def forward(ctx, d, bins, distance, sigma, offset):
         dc = d.contiguous()
-        ctx.d, ctx.args = dc, (bins, distance, sigma, offset)
+        ctx.d, ctx.d_in, ctx.args = dc, d, (bins, distance, sigma, offset)
         out = torch.empty(tuple(dc.shape[:-1]) + (bins,), dtype=torch.float32, device=d.device)
         _ffi.call("mp_gauss_basis_f32", _ffi.ptr(dc), dc.numel(), bins, distance, sigma, offset, _ffi.ptr(out),
                   _ffi.stream())
@@ -411,11 +668,38 @@ class GaussBasis(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
+        if torch.is_grad_enabled():
+            return GaussBasisAdjoint.apply(ctx.d_in, g, ctx.args), None, None, None, None
+        return _gauss_basis_grad(ctx.d, g.contiguous(), ctx.args), None, None, None, None
+
+
+def _gauss_basis_grad(dc, gc, args):
+    bins, distance, sigma, offset = args
+    gd = torch.empty_like(dc)
+    _ffi.call("mp_gauss_basis_grad_f32", _ffi.ptr(dc), dc.numel(), bins, distance, sigma, offset, _ffi.ptr(gc),
+              _ffi.ptr(gd), _ffi.stream())
+    return gd
+
+
+class GaussBasisAdjoint(torch.autograd.Function):
+    """gd = sum_k g_k phi_k'(d) as an op of (d, g); reverse on mp_gauss_basis_grad2_f32."""
+
+    @staticmethod
+    def forward(ctx, d, g, args):
+        dc, gc = d.contiguous(), g.contiguous()
+        ctx.dc, ctx.gc, ctx.args = dc, gc, args
+        return _gauss_basis_grad(dc, gc, args)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, h):
         bins, distance, sigma, offset = ctx.args
-        gd = torch.empty_like(ctx.d)
-        _ffi.call("mp_gauss_basis_grad_f32", _ffi.ptr(ctx.d), ctx.d.numel(), bins, distance, sigma, offset,
-                  _ffi.ptr(g.contiguous()), _ffi.ptr(gd), _ffi.stream())
-        return gd, None, None, None, None
+        hc = h.contiguous()
+        d_bar = torch.empty_like(ctx.dc) if ctx.needs_input_grad[0] else None
+        g_bar = torch.empty_like(ctx.gc) if ctx.needs_input_grad[1] else None
+        _ffi.call("mp_gauss_basis_grad2_f32", _ffi.ptr(ctx.dc), ctx.dc.numel(), bins, distance, sigma, offset,
+                  _ffi.ptr(ctx.gc), _ffi.ptr(hc), _ffi.ptr(d_bar), _ffi.ptr(g_bar), _ffi.stream())
+        return d_bar, g_bar, None
 
 
 class CosCutoff(torch.autograd.Function):
@@ -428,6 +712,7 @@ class CosCutoff(torch.autograd.Function):
         return out
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, g):
         gd = torch.empty_like(ctx.d)
         _ffi.call("mp_cos_cutoff_grad_f32", _ffi.ptr(ctx.d), ctx.d.numel(), float(ctx.cutoff),

@@ -117,3 +117,22 @@ __device__ __forceinline__ float mp_act_grad(int act, float alpha, float x) {
     default: return 1.0f;
   }
 }
+
+// d^2 act / d pre-activation^2, for every code mp_act_grad handles (csrc/mp_backward2.hip: reverse of the activation
+// derivative when the loss holds forces).  Piecewise-linear activations (relu, leaky relu, linear) give 0.
+// sigma (1 - sigma) is taken as sigma(x) sigma(-x): 1 - sigma(x) cancels to a few bits for large x.
+__device__ __forceinline__ float mp_act_grad2(int act, float alpha, float x) {
+  switch (act) {
+    case MP_ACT_SHIFTED_SOFTPLUS:
+    case MP_ACT_SOFTPLUS2:
+    case MP_ACT_SOFTPLUS: return mp_sigmoid(x) * mp_sigmoid(-x);
+    case MP_ACT_SWISH: {
+      const float s = mp_sigmoid(x), sm = mp_sigmoid(-x);
+      return s * sm * (2.0f + x * (sm - s));
+    }
+    case MP_ACT_SIGMOID: { const float s = mp_sigmoid(x), sm = mp_sigmoid(-x); return s * sm * (sm - s); }
+    case MP_ACT_TANH: { const float t = tanhf(x); return -2.0f * t * (1.0f - t * t); }
+    case MP_ACT_SELU: return x > 0.0f ? 0.0f : 1.05070098f * 1.67326324f * expf(x);
+    default: return 0.0f;  // relu, leaky relu, linear
+  }
+}

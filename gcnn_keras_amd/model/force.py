@@ -7,6 +7,10 @@ here ``torch.autograd`` is the tape and every forward / backward computation is 
 (``gcnn_keras_amd.autograd``).  The fork's QM/MM inputs are honoured: with ``esp_input`` / ``esp_grad_input`` named, the
 force gains the chain term ``dE/desp * desp/dr`` (force.py:153-158, 179-186).  Energy models that bring a fused reverse
 pass (PaiNN: ``gcnn_keras_amd/fused_painn.py``) skip the tape altogether: energy and forces come from one HIP graph.
+
+Training (the fork's force_schnet.py:163-205, 262): ``compile(optimizer, loss=[energy, force], loss_weights)`` then
+``train_on_batch(x, [energy, force])``.  The force enters the loss, so the reverse pass is recorded itself
+(``create_graph=True``) and differentiated once more: the second-order rules of ``gcnn_keras_amd.autograd``.
 """
 import importlib
 
@@ -64,6 +68,24 @@ class EnergyForceModel:
         fused = self._fused_energy_force(inputs, kwargs)
         if fused is not None:
             return fused
+        outputs, eng, de_dr = self._tape(inputs, kwargs)
+        force = x.with_values(de_dr.contiguous())
+        if self.output_to_tensor:
+            force = self.cast_coordinates(force)
+        eng = eng.detach()
+        if self.output_as_dict:
+            return {"energy": eng, "force": force}
+        if isinstance(outputs, list):
+            return [o.detach() if torch.is_tensor(o) else o for o in outputs] + [force]
+        return eng, force
+
+    predict = __call__
+
+    def _tape(self, inputs, kwargs, create_graph=False):
+        """Energy model on the tape, then ``de_dr`` = the flat force values ``(N, 3[, states])`` with the wrapper's sign
+        and state-axis conventions.  ``create_graph``: the reverse pass is recorded too (a loss on the force)."""
+        from ..autograd import input_grads_only
+        x = inputs[self.coordinate_input]
         inputs_energy = list(inputs)
         x_req = x.values.detach().clone().requires_grad_(True)
         inputs_energy[self.coordinate_input] = x.with_values(x_req)
@@ -84,13 +106,15 @@ class EnergyForceModel:
                 eng = eng.unsqueeze(-1)
             states = int(eng.shape[1])
             grads, grads_esp = [], []
-            for s in range(states):
-                g = torch.autograd.grad(eng[:, s], watched, grad_outputs=torch.ones_like(eng[:, s]),
-                                        retain_graph=s + 1 < states, allow_unused=True)
-                grads.append(g[0] if g[0] is not None else torch.zeros_like(x_req))
-                if with_esp:
-                    grads_esp.append(g[1] if g[1] is not None else torch.zeros_like(esp_req))
-        de_dr = torch.stack(grads, dim=-1)  # (N, 3, states)
+            with input_grads_only():   # dE/dx only: the rules skip the weight gradients torch would throw away
+                for s in range(states):
+                    g = torch.autograd.grad(eng[:, s], watched, grad_outputs=torch.ones_like(eng[:, s]),
+                                            retain_graph=create_graph or s + 1 < states, create_graph=create_graph,
+                                            allow_unused=True)
+                    grads.append(g[0] if g[0] is not None else torch.zeros_like(x_req))
+                    if with_esp:
+                        grads_esp.append(g[1] if g[1] is not None else torch.zeros_like(esp_req))
+            de_dr = torch.stack(grads, dim=-1)  # (N, 3, states)
         if with_esp:
             # dE/dr += dE/desp * desp/dr (force.py:179-186): (N, 1, states) x (N, 3, 1) on the engine's broadcast kernel
             from .. import _ffi
@@ -103,17 +127,89 @@ class EnergyForceModel:
             de_dr = -de_dr
         if self.output_squeeze_states:
             de_dr = de_dr.squeeze(-1)
-        force = x.with_values(de_dr.contiguous())
-        if self.output_to_tensor:
-            force = self.cast_coordinates(force)
-        eng = eng.detach()
-        if self.output_as_dict:
-            return {"energy": eng, "force": force}
-        if isinstance(outputs, list):
-            return [o.detach() if torch.is_tensor(o) else o for o in outputs] + [force]
-        return eng, force
+        return outputs, eng, de_dr
 
-    predict = __call__
+    # -- training --------------------------------------------------------------------------------------------------------
+    @property
+    def trainable_weights(self):
+        """The energy model's weight tensors (``Model.trainable_weights``)."""
+        return self.energy_model.trainable_weights
+
+    def requires_grad_(self, flag=True):
+        self.energy_model.requires_grad_(flag)
+        return self
+
+    def compile(self, optimizer="adam", loss="mean_absolute_error", loss_weights=None, clipnorm=None):
+        """Keras ``compile`` of the two-output model (energy, force), in the order the wrapper returns them.
+
+        ``loss``: one name or callable for both outputs, or a list / tuple of two (``"mean_absolute_error"``,
+        ``"mean_squared_error"``, ...; see ``model.losses``).  ``loss_weights``: two floats, default ``[1, 1]``; the total
+        loss is ``sum_i w_i loss_i`` (Keras).  ``optimizer``: ``"adam"`` / ``"sgd"`` with Keras' defaults or a
+        ``torch.optim.Optimizer`` over ``trainable_weights``.  ``clipnorm``: every gradient tensor is clipped to this L2
+        norm before the step (Keras OptimizerV2; the fork uses 1.0)."""
+        from .losses import get_loss
+        from .utils import check_clipnorm, make_optimizer
+        losses = list(loss) if isinstance(loss, (list, tuple)) else [loss, loss]
+        if len(losses) != 2:
+            raise ValueError("EnergyForceModel has two outputs (energy, force): expected 2 losses, got %d" % len(losses))
+        loss_fns = [get_loss(name) for name in losses]
+        weights = [1.0, 1.0] if loss_weights is None else loss_weights
+        if not isinstance(weights, (list, tuple)) or len(weights) != 2:
+            raise ValueError("loss_weights must hold one weight per output (energy, force), got %r" % (loss_weights,))
+        self.optimizer = make_optimizer(optimizer, self.trainable_weights)
+        self.loss, self.loss_weights = losses, [float(w) for w in weights]
+        self._loss_fns, self.clipnorm = loss_fns, check_clipnorm(clipnorm)
+        return self
+
+    def train_on_batch(self, x, y, sample_weight=None):
+        """One optimizer step on ``x`` and ``y = [energy, force]``; returns ``[total, energy_loss, force_loss]`` (floats,
+        before the step), as Keras does for a two-output model.
+
+        The step: the energy model's layer path with every weight requiring grad, ``F = +-dE/dx`` recorded on the tape
+        (``create_graph=True``; sign, ``energy_output`` and ``output_squeeze_states`` as in ``__call__``), the weighted
+        loss, its gradient through the forward AND the reverse pass (second-order rules of ``gcnn_keras_amd.autograd``),
+        optional clipping, ``optimizer.step()``; ``requires_grad`` of the weights is restored afterwards.
+
+        Energy target: ``(batch, states)`` or ``(batch,)``.  Force target: a ``RaggedTensor`` with the coordinates' row
+        splits, its flat ``(N, 3)`` values, or a padded ``(batch, Nmax, 3)`` array (unpadded with the coordinates' row
+        splits).  The force loss is Keras' ragged reduction: the mean over the 3 components of an atom, then the mean over
+        the N real atoms of the batch; padding never counts.  ``sample_weight``: ``None``, or ``[w_energy, None]`` with one
+        weight per graph for the energy loss; weights on the force output (also a single array, which Keras would apply
+        to both outputs) raise ``NotImplementedError``.  The QM/MM ``esp_input`` / ``esp_grad_input`` branch raises
+        ``NotImplementedError`` as well."""
+        from .losses import flat_target
+        if getattr(self, "optimizer", None) is None:
+            raise RuntimeError("EnergyForceModel: call compile(optimizer, loss) before train_on_batch")
+        if self.esp_input is not None and self.esp_grad_input is not None:
+            raise NotImplementedError("training through the QM/MM esp branch is not implemented")
+        if not isinstance(y, (list, tuple)) or len(y) != 2:
+            raise ValueError("y must be [energy, force]")
+        sw_energy = None
+        if sample_weight is not None:
+            if not isinstance(sample_weight, (list, tuple)) or len(sample_weight) != 2 or sample_weight[1] is not None:
+                raise NotImplementedError("sample_weight on the force output is not implemented; pass [w_energy, None]")
+            sw_energy = sample_weight[0]
+        weights = self.trainable_weights
+        saved = [t.requires_grad for t in weights]
+        try:
+            for t in weights:
+                t.requires_grad_(True)
+            self.optimizer.zero_grad(set_to_none=True)
+            with torch.enable_grad():
+                _, eng, de_dr = self._tape(x, {}, create_graph=True)
+                coords = x[self.coordinate_input]
+                f_true = flat_target(y[1], de_dr, coords.row_splits_host())
+                loss_e = self._loss_fns[0](eng, y[0], sw_energy)
+                loss_f = self._loss_fns[1](de_dr, f_true, None)
+                total = loss_e * self.loss_weights[0] + loss_f * self.loss_weights[1]
+                total.backward(inputs=[t for t in weights])
+            from .utils import clip_gradients
+            clip_gradients(weights, self.clipnorm)
+            self.optimizer.step()
+        finally:
+            for t, flag in zip(weights, saved):
+                t.requires_grad_(flag)
+        return [float(total.detach()), float(loss_e.detach()), float(loss_f.detach())]
 
     def _fused_energy_force(self, inputs, kwargs=None):
         """Energy models that bring a fused reverse pass (``model.fused.energy_force``: PAiNN, gcnn_keras_amd/fused_painn.py)

@@ -47,6 +47,26 @@ def categorical_crossentropy(y_pred, y_true, sample_weight=None):
     return _reduce(-(t * p.log()).sum(dim=-1), sample_weight)
 
 
+def flat_target(target, like, row_splits_host):
+    """A per-atom target as the flat ``(N, ...)`` values of ``like`` (the model's flat output): a ``RaggedTensor`` gives
+    its values, a flat array is taken as it is, a padded ``(B, Nmax, ...)`` array (one axis more than ``like``) is
+    unpadded with the input's row splits, so that padding never enters a loss."""
+    t = _values(target, like)
+    if t.dim() == like.dim() + 1:
+        splits = np.asarray(row_splits_host, dtype=np.int64)
+        counts = splits[1:] - splits[:-1]
+        if int(t.shape[0]) != counts.size or (counts.size and int(counts.max()) > int(t.shape[1])):
+            raise ValueError("padded target of shape %s does not fit row splits with %d rows of at most %d atoms"
+                             % (tuple(t.shape), counts.size, int(counts.max()) if counts.size else 0))
+        graph = np.repeat(np.arange(counts.size, dtype=np.int64), counts)
+        local = np.arange(int(splits[-1]), dtype=np.int64) - splits[:-1][graph]
+        t = t[torch.from_numpy(graph).to(t.device), torch.from_numpy(local).to(t.device)]
+    t = t.to(device=like.device, dtype=like.dtype)
+    if t.numel() != like.numel():
+        raise ValueError("target of shape %s does not match the output %s" % (tuple(t.shape), tuple(like.shape)))
+    return t.reshape(like.shape)
+
+
 _LOSSES = {"mean_absolute_error": mean_absolute_error, "mae": mean_absolute_error,
            "mean_squared_error": mean_squared_error, "mse": mean_squared_error,
            "categorical_crossentropy": categorical_crossentropy}

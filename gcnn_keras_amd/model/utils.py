@@ -58,6 +58,45 @@ def update_model_kwargs(model_default, update_recursive=inf):
     return decorate
 
 
+def make_optimizer(optimizer, weights):
+    """``"adam"`` / ``"sgd"`` with Keras' defaults (Adam lr 1e-3, betas (0.9, 0.999), epsilon 1e-7; SGD lr 0.01) over
+    ``weights``, or a ``torch.optim.Optimizer`` as given."""
+    import torch
+    if isinstance(optimizer, str):
+        name = optimizer.lower()
+        if name == "adam":
+            return torch.optim.Adam(weights, lr=1e-3, betas=(0.9, 0.999), eps=1e-7)
+        if name == "sgd":
+            return torch.optim.SGD(weights, lr=0.01)
+        raise ValueError("Unknown optimizer %r (use 'adam', 'sgd' or a torch.optim.Optimizer)" % (optimizer,))
+    if not isinstance(optimizer, torch.optim.Optimizer):
+        raise ValueError("optimizer must be 'adam', 'sgd' or a torch.optim.Optimizer, got %r" % (optimizer,))
+    return optimizer
+
+
+def check_clipnorm(clipnorm):
+    if clipnorm is None:
+        return None
+    clipnorm = float(clipnorm)
+    if not clipnorm > 0.0:
+        raise ValueError("clipnorm must be positive, got %r" % (clipnorm,))
+    return clipnorm
+
+
+def clip_gradients(weights, clipnorm):
+    """Keras OptimizerV2 ``clipnorm`` (``tf.clip_by_norm`` per gradient tensor): g * c / max(|g|_2, c).  Optimizer
+    plumbing on the gradients, in place; nothing happens for ``clipnorm=None``."""
+    if clipnorm is None:
+        return
+    import torch
+    for t in weights:
+        g = t.grad
+        if g is None:
+            continue
+        norm = g.square().sum().sqrt()
+        g.copy_(g * clipnorm / torch.clamp(norm, min=clipnorm))
+
+
 class Model:
     """Minimal stand-in for ``ks.models.Model``: an ordered list of layers plus a forward function.
 
@@ -87,6 +126,7 @@ class Model:
         self.optimizer = None
         self.loss = None
         self._loss_fn = None
+        self.clipnorm = None
 
     def __call__(self, inputs, **kwargs):
         if self.auto_graph and not kwargs and not self._weights_need_grad():
@@ -180,24 +220,15 @@ class Model:
         return [t.detach().cpu().numpy() for _, t in self.weights]
 
     # -- training --------------------------------------------------------------------------------------------------------
-    def compile(self, optimizer="adam", loss="mean_absolute_error"):
+    def compile(self, optimizer="adam", loss="mean_absolute_error", clipnorm=None):
         """``optimizer``: a ``torch.optim.Optimizer`` over ``trainable_weights``, or ``"adam"`` / ``"sgd"`` with Keras'
         defaults (Adam lr 1e-3, betas (0.9, 0.999), epsilon 1e-7; SGD lr 0.01).  ``loss``: ``"mean_absolute_error"``,
-        ``"mean_squared_error"`` or ``"categorical_crossentropy"`` (Keras semantics, reduction sum over batch size)."""
-        import torch
+        ``"mean_squared_error"`` or ``"categorical_crossentropy"`` (Keras semantics, reduction sum over batch size).
+        ``clipnorm``: clip every gradient tensor to this L2 norm before the step (Keras OptimizerV2 ``clipnorm``)."""
         from .losses import get_loss
         loss_fn = get_loss(loss)
-        if isinstance(optimizer, str):
-            name = optimizer.lower()
-            if name == "adam":
-                optimizer = torch.optim.Adam(self.trainable_weights, lr=1e-3, betas=(0.9, 0.999), eps=1e-7)
-            elif name == "sgd":
-                optimizer = torch.optim.SGD(self.trainable_weights, lr=0.01)
-            else:
-                raise ValueError("Unknown optimizer %r (use 'adam', 'sgd' or a torch.optim.Optimizer)" % (optimizer,))
-        elif not isinstance(optimizer, torch.optim.Optimizer):
-            raise ValueError("optimizer must be 'adam', 'sgd' or a torch.optim.Optimizer, got %r" % (optimizer,))
-        self.optimizer, self.loss, self._loss_fn = optimizer, loss, loss_fn
+        self.optimizer = make_optimizer(optimizer, self.trainable_weights)
+        self.loss, self._loss_fn, self.clipnorm = loss, loss_fn, check_clipnorm(clipnorm)
         return self
 
     def train_on_batch(self, x, y, sample_weight=None):
@@ -215,6 +246,7 @@ class Model:
                 pred = self._forward(x)
                 loss = self._loss_fn(pred, y, sample_weight)
                 loss.backward()
+            clip_gradients(weights, getattr(self, "clipnorm", None))
             self.optimizer.step()
         finally:
             for t, flag in zip(weights, saved):
