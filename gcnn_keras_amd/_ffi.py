@@ -149,6 +149,17 @@ _SIGNATURES = {
     "mp_memcpy_h2d_async": [P, P, c_size_t, P],
     "mp_gcn_tile_f32": [P, P],
     "mp_concat_batches": [P, P],
+    "mp_acsf_grad_ws_bytes": [c_int64, c_int, P],
+    "mp_acsf_g2_f32": [P, P, c_int64, P, c_int64, P, P, P, P, c_int, c_int, c_int, P, P],
+    "mp_acsf_g4_f32": [P, P, c_int64, P, c_int64, P, P, P, P, P, c_int, c_int, c_int, c_float, P, P],
+    "mp_acsf_g2_jvp_f32": [P, P, c_int64, P, c_int64, P, P, P, P, c_int, c_int, c_int, P, P, P],
+    "mp_acsf_g4_jvp_f32": [P, P, c_int64, P, c_int64, P, P, P, P, P, c_int, c_int, c_int, c_float, P, P, P],
+    "mp_acsf_g2_grad_f32": [P, P, c_int64, P, c_int64, P, P, P, P, P, P, c_int, c_int, c_int, P, P, c_size_t, P, P],
+    "mp_acsf_g4_grad_f32": [P, P, c_int64, P, c_int64, P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_float, P, P,
+                            c_size_t, P, P],
+    "mp_relational_dense_f32": [P, c_int64, c_int64, P, c_int64, P, P, c_int64, c_int, c_float, c_int, P, P, P, P],
+    "mp_relational_dense_wgrad_ws_bytes": [c_int64, c_int64, P],
+    "mp_relational_dense_wgrad_f32": [P, c_int64, c_int64, P, c_int64, P, c_int64, P, P, P, c_size_t, P],
 }
 _RESTYPES = {"mp_last_error": c_char_p}
 

@@ -538,18 +538,36 @@ class ConcatLast(torch.autograd.Function):
         return _concat_last_raw(list(values))
 
     @staticmethod
-    @once_differentiable
     def backward(ctx, g):
-        gc = g.contiguous()
-        total = int(gc.shape[-1])
-        rows = gc.numel() // max(total, 1)
-        outs, off = [], 0
-        for w in ctx.widths:
-            o = torch.empty(tuple(gc.shape[:-1]) + (w,), dtype=gc.dtype, device=gc.device)
-            _ffi.call("mp_copy_cols_f32", _ffi.ptr(gc), total, off, _ffi.ptr(o), w, 0, rows, w, _ffi.stream())
-            outs.append(o)
-            off += w
-        return tuple(outs)
+        if torch.is_grad_enabled():     # a force pass through LazyConcatenate (HDNNP2nd): the reverse is recorded too
+            return SplitWidths.apply(g, tuple(ctx.widths))
+        return tuple(_split_widths(g, ctx.widths))
+
+
+def _split_widths(g, widths):
+    """ConcatLast's reverse: the column blocks of ``g`` as contiguous tensors."""
+    gc = g.contiguous()
+    total = int(gc.shape[-1])
+    rows = gc.numel() // max(total, 1)
+    outs, off = [], 0
+    for w in widths:
+        o = torch.empty(tuple(gc.shape[:-1]) + (w,), dtype=gc.dtype, device=gc.device)
+        _ffi.call("mp_copy_cols_f32", _ffi.ptr(gc), total, off, _ffi.ptr(o), w, 0, rows, w, _ffi.stream())
+        outs.append(o)
+        off += w
+    return outs
+
+
+class SplitWidths(torch.autograd.Function):
+    """ConcatLast's backward as a differentiable op of ``g``; its own backward is the concatenation again."""
+
+    @staticmethod
+    def forward(ctx, g, widths):
+        return tuple(_split_widths(g, widths))
+
+    @staticmethod
+    def backward(ctx, *hs):
+        return ConcatLast.apply(*[h.contiguous() for h in hs]), None
 
 
 class SplitLast(torch.autograd.Function):
@@ -559,8 +577,9 @@ class SplitLast(torch.autograd.Function):
         return tuple(_split_last_raw(value, num))
 
     @staticmethod
-    @once_differentiable
     def backward(ctx, *gs):
+        if torch.is_grad_enabled():     # the concatenation is differentiable itself
+            return ConcatLast.apply(*[g.contiguous() for g in gs]), None
         from .layers.modules import _concat_last_raw
         return _concat_last_raw([g.contiguous() for g in gs]), None
 
@@ -718,3 +737,160 @@ class CosCutoff(torch.autograd.Function):
         _ffi.call("mp_cos_cutoff_grad_f32", _ffi.ptr(ctx.d), ctx.d.numel(), float(ctx.cutoff),
                   _ffi.ptr(g.contiguous()), _ffi.ptr(gd), _ffi.stream())
         return gd, None
+
+
+# ------------------------------------------------------------------------------------------------ HDNNP2nd
+_coordinate_hessian_discarded = [False]
+
+
+@contextlib.contextmanager
+def coordinate_hessian_discarded():
+    """Set by ``EnergyForceModel.train_on_batch`` around ``total.backward(inputs=weights)``: there the second derivative of
+    the symmetry functions with respect to the coordinates would only reach the coordinate leaf, which the step
+    discards, so the ACSF adjoint may skip it.  Everywhere else asking for it raises ``NotImplementedError``."""
+    prev = _coordinate_hessian_discarded[0]
+    _coordinate_hessian_discarded[0] = True
+    try:
+        yield
+    finally:
+        _coordinate_hessian_discarded[0] = prev
+
+
+class ACSF(torch.autograd.Function):
+    """ACSFG2 / ACSFG4 of coordinates (N, 3) -> (N, R*m) on csrc/mp_acsf.hip; ``spec`` (layers/conv/acsf_conv.py) holds
+    the atomic numbers, index plan and tables.  Backward: ``mp_acsf_g*_grad_f32``; in grad mode ``ACSFAdjoint``."""
+
+    @staticmethod
+    def forward(ctx, xyz, spec):
+        ctx.spec, ctx.xyz = spec, xyz
+        return spec.forward(xyz)
+
+    @staticmethod
+    def backward(ctx, g):
+        if torch.is_grad_enabled():
+            return ACSFAdjoint.apply(ctx.xyz, g, ctx.spec), None
+        return ctx.spec.grad(ctx.xyz.detach(), g), None
+
+
+class ACSFAdjoint(torch.autograd.Function):
+    """dx = sum_m g dG_m/dx as an op of (x, g).  It is linear in g: g_bar = dG/dx . h on the JVP kernels
+    (``mp_acsf_g*_jvp_f32``).  x_bar, the second derivative of G with respect to the coordinates, is not implemented:
+    asking for it raises, except under ``coordinate_hessian_discarded()``, where it is skipped."""
+
+    @staticmethod
+    def forward(ctx, xyz, g, spec):
+        ctx.spec, ctx.xyz = spec, xyz.detach()
+        return spec.grad(ctx.xyz, g)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, h):
+        if ctx.needs_input_grad[0] and not _coordinate_hessian_discarded[0]:
+            raise NotImplementedError("the second derivative of the symmetry functions with respect to the coordinates "
+                                      "(a Hessian through ACSFG2 / ACSFG4) is not implemented")
+        g_bar = ctx.spec.jvp(ctx.xyz, h) if ctx.needs_input_grad[1] else None
+        return None, g_bar, None
+
+
+def _relational_backward(gc, x, kernel, rel, pre, act, alpha, want_x, want_w, want_b):
+    """First-order RelationalDense backward: (dx, dW, db, gp) with gp = dy * act'(pre)."""
+    from .layers.relational import relational_dense_t_raw, relational_wgrad
+    if pre is not None:
+        gp = torch.empty_like(gc)
+        _ffi.call("mp_activation_grad_f32", act, float(alpha), _ffi.ptr(pre), _ffi.ptr(gc), gc.numel(), _ffi.ptr(gp),
+                  _ffi.stream())
+        gc = gp
+    gx = gw = gb = None
+    if want_x:
+        gx = relational_dense_t_raw(gc, kernel, rel)
+    if want_w or want_b:
+        gw, gb = relational_wgrad(x, gc, rel, int(kernel.shape[0]), with_kernel=want_w, with_bias=want_b)
+    return gx, gw, gb, gc
+
+
+class RelationalDense(torch.autograd.Function):
+    """y = act(x W[rel] + b) (mp_relational_dense_f32); backward gp = dy * act'(pre), dx = gp W[rel]^T,
+    dW[q] = x_q^T gp_q, db = sum gp, each only when asked.  In grad mode the backward is ``RelationalDenseAdjoint``."""
+
+    @staticmethod
+    def forward(ctx, x, kernel, bias, rel, act_code, alpha):
+        from .layers.relational import relational_dense_raw
+        pre, y = relational_dense_raw(x, kernel, bias, rel, act_code, alpha, keep_pre=act_code != 0)
+        ctx.kernel, ctx.bias, ctx.rel, ctx.act, ctx.alpha, ctx.pre = kernel, bias, rel, act_code, alpha, pre
+        ctx.x = x if (ctx.needs_input_grad[1] or ctx.needs_input_grad[0]) else None
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        want_x = ctx.needs_input_grad[0]
+        want_w = ctx.needs_input_grad[1] and not _input_grads_only[0]
+        want_b = ctx.needs_input_grad[2] and not _input_grads_only[0]
+        if torch.is_grad_enabled():
+            gx, gw, gb = RelationalDenseAdjoint.apply(g, ctx.x, ctx.kernel, ctx.bias, ctx.rel, ctx.pre, ctx.act,
+                                                      ctx.alpha, want_x, want_w, want_b)
+            return gx, gw, gb, None, None, None
+        gx, gw, gb, _ = _relational_backward(g.contiguous(), ctx.x, ctx.kernel, ctx.rel, ctx.pre, ctx.act, ctx.alpha,
+                                             want_x, want_w, want_b)
+        return gx, gw, gb, None, None, None
+
+
+class RelationalDenseAdjoint(torch.autograd.Function):
+    """RelationalDense's backward (dx, dW, db) as an op of (dy, x, W, b) - ``DenseAdjoint`` with the relational kernels:
+    h_gp = hx W[rel] + x hW[rel] + hb; dy_bar = h_gp act'(pre), pre_bar = h_gp dy act''(pre);
+    x_bar = gp hW[rel]^T + pre_bar W[rel]^T,  W_bar = wgrad(hx, gp) + wgrad(x, pre_bar),  b_bar = sum_rows pre_bar."""
+
+    @staticmethod
+    def forward(ctx, g, x, kernel, bias, rel, pre, act, alpha, want_x, want_w, want_b):
+        ctx.set_materialize_grads(False)
+        gc = g.contiguous()
+        gx, gw, gb, gp = _relational_backward(gc, x, kernel, rel, pre, act, alpha, want_x, want_w, want_b)
+        ctx.g, ctx.x, ctx.kernel, ctx.rel, ctx.pre, ctx.gp, ctx.act, ctx.alpha = gc, x, kernel, rel, pre, gp, act, alpha
+        return gx, gw, gb
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, hx, hw, hb):
+        from .layers.modules import _binary_raw
+        from .layers.relational import relational_dense_raw, relational_dense_t_raw, relational_wgrad
+        need_g, need_x, need_w, need_b = ctx.needs_input_grad[:4]
+        x, kernel, rel, pre, gp = ctx.x, ctx.kernel, ctx.rel, ctx.pre, ctx.gp
+        nrel, u = int(kernel.shape[0]), int(kernel.shape[2])
+        h_gp = None
+        if hx is not None:
+            h_gp = relational_dense_raw(hx.contiguous(), kernel, None, rel, 0, 0.0)[1]
+        if hw is not None:
+            h_gp = _add(h_gp, relational_dense_raw(x, hw.contiguous(), hb.contiguous() if hb is not None else None,
+                                                   rel, 0, 0.0)[1])
+        elif hb is not None:
+            rows = gp.numel() // max(u, 1)
+            zero = torch.zeros((rows, u), dtype=torch.float32, device=gp.device)
+            h_gp = _add(h_gp, _binary_raw(_ffi.MP_ADD, zero, hb.contiguous().view(1, u)).view(gp.shape))
+        if h_gp is None:
+            return (None,) * 11
+        g_bar = pre_bar = None
+        if pre is None:
+            g_bar = h_gp if need_g else None      # linear: act'' = 0, no pre-activation term
+        else:
+            if need_g:
+                g_bar = torch.empty_like(h_gp)
+            if need_x or need_w or need_b:
+                pre_bar = torch.empty_like(h_gp)
+            _ffi.call("mp_activation_grad2_f32", ctx.act, float(ctx.alpha), _ffi.ptr(pre), _ffi.ptr(ctx.g),
+                      _ffi.ptr(h_gp), _ffi.ptr(pre_bar), _ffi.ptr(g_bar), h_gp.numel(), _ffi.stream())
+        x_bar = w_bar = b_bar = None
+        if need_x:
+            if hw is not None:
+                x_bar = relational_dense_t_raw(gp, hw.contiguous(), rel)
+            if pre_bar is not None:
+                x_bar = _add(x_bar, relational_dense_t_raw(pre_bar, kernel, rel))
+        if need_w:
+            if hx is not None:
+                w_bar = relational_wgrad(hx, gp, rel, nrel, with_bias=False)[0]
+            if pre_bar is not None:
+                w_pre, b_bar = relational_wgrad(x, pre_bar, rel, nrel, with_bias=need_b)
+                w_bar = _add(w_bar, w_pre)
+        if need_b and b_bar is None and pre_bar is not None:
+            b_bar = _sum_rows(pre_bar)
+        if not need_b:
+            b_bar = None
+        return g_bar, x_bar, w_bar, b_bar, None, None, None, None, None, None, None

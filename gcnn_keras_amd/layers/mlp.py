@@ -112,3 +112,57 @@ class MLP(MLPBase):
 
 
 GraphMLP = MLP
+
+
+class RelationalMLP(MLPBase):
+    r"""Stack of RelationalDense layers with activations (kgcnn/layers/mlp.py:328-416): inputs ``[features,
+    relations]``, every layer picks its kernel by the row's relation.  Normalisation raises ``NotImplementedError`` (as
+    ``MLP``'s batch techniques do); dropout is the identity outside training and raises in a training forward."""
+
+    def __init__(self, units, num_relations: int, num_bases: int = None, num_blocks: int = None, **kwargs):
+        from .relational import RelationalDense
+        super().__init__(units=units, **kwargs)
+        if num_bases is not None or num_blocks is not None:
+            raise NotImplementedError("RelationalMLP with num_bases / num_blocks is not implemented")
+        self._conf_num_relations = num_relations
+        self._conf_num_bases = num_bases
+        self._conf_num_blocks = num_blocks
+        self._conf_relational_kwargs = {"num_relations": num_relations, "num_bases": num_bases,
+                                        "num_blocks": num_blocks}
+        if any(self._conf_use_normalization):
+            raise NotImplementedError("normalisation inside RelationalMLP is not implemented")
+        self.mlp_dense_layer_list = [
+            RelationalDense(units=self._conf_units[i], num_relations=num_relations, use_bias=self._conf_use_bias[i],
+                            activation="linear", kernel_initializer=self._conf_kernel_initializer[i],
+                            bias_initializer=self._conf_bias_initializer[i], name=self.name + "_dense_" + str(i))
+            for i in range(self._depth)]
+        self.mlp_activation_layer_list = [
+            Activation(activation=self._conf_activation[i], name=self.name + "_act_" + str(i))
+            for i in range(self._depth)]
+
+    def build(self, input_shape):
+        super().build(input_shape)
+        shape, rel_shape = tuple(input_shape[0]), tuple(input_shape[1])
+        for i in range(self._depth):
+            self.mlp_dense_layer_list[i].ensure_built([shape, rel_shape])
+            shape = shape[:-1] + (self._conf_units[i],)
+
+    def call(self, inputs, **kwargs):
+        x, relations = inputs
+        if any(self._conf_use_dropout) and kwargs.get("training"):
+            raise NotImplementedError("dropout in a training forward is outside the hot path")
+        for i in range(self._depth):
+            # RelationalDense(linear) followed by Activation is one kernel with the activation in its epilogue
+            d = self.mlp_dense_layer_list[i]
+            saved = d.activation
+            d.activation = self.mlp_activation_layer_list[i].activation
+            try:
+                x = d([x, relations], **kwargs)
+            finally:
+                d.activation = saved
+        return x
+
+    def get_config(self):
+        config = super().get_config()
+        config.update(self._conf_relational_kwargs)
+        return config

@@ -202,7 +202,9 @@ class EnergyForceModel:
                 loss_e = self._loss_fns[0](eng, y[0], sw_energy)
                 loss_f = self._loss_fns[1](de_dr, f_true, None)
                 total = loss_e * self.loss_weights[0] + loss_f * self.loss_weights[1]
-                total.backward(inputs=[t for t in weights])
+                from ..autograd import coordinate_hessian_discarded
+                with coordinate_hessian_discarded():   # only the weights' gradients are kept (HDNNP2nd's ACSF rules)
+                    total.backward(inputs=[t for t in weights])
             from .utils import clip_gradients
             clip_gradients(weights, self.clipnorm)
             self.optimizer.step()

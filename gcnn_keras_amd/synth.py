@@ -248,3 +248,97 @@ def gcn_params(seed=9, depth=3, in_features=1433, units=64, out_units=(64, 32, 7
         p["output_mlp/%d/bias" % k] = bias(u)
         fan = u
     return p
+
+
+# ---------------------------------------------------------------------------------------------------------- HDNNP2nd
+BOHR_PER_ANGSTROM = 1.8897261246257702
+# Alanine dipeptide, C6 H12 N2 O2 (the fork's force_hdnnp2nd.py dataset "Alanindipeptide")
+ALANINE_DIPEPTIDE_Z = np.array([1, 6, 1, 1, 6, 8, 7, 1, 6, 1, 6, 1, 1, 1, 6, 8, 7, 1, 6, 1, 1, 1], dtype=np.int64)
+
+# The fork's symmetry-function and network table (force_hdnnp2nd.py:43-65): distances in Bohr.
+HDNNP_FORK = {
+    "cutoff_rad": 20.0, "rs": [0.0, 3.0, 4.0, 5.0, 6.0, 7.0, 8.0], "eta": [0.03, 0.08, 0.16, 0.3, 0.5],
+    "cutoff_ang": 12.0, "lamda": [-1.0, 1.0], "zeta": [1.0, 2.0, 4.0, 8.0, 16.0], "eta_ang": [0.03, 0.08, 0.16, 0.3, 0.5],
+    "max_elements": 30, "elements": [1, 6, 7, 8], "hidden": [35, 35], "hidden_activation": ["tanh", "tanh"],
+    "multiplicity": 2.0,
+}
+
+
+def hdnnp_model_kwargs(fork=HDNNP_FORK):
+    """``make_model_behler`` keyword arguments of the fork's force_hdnnp2nd.py:139-174 (custom tanh as "tanh")."""
+    return {
+        "g2_kwargs": {"eta": list(fork["eta"]), "rs": list(fork["rs"]), "rc": fork["cutoff_rad"],
+                      "elements": list(fork["elements"])},
+        "g4_kwargs": {"eta": list(fork["eta_ang"]), "zeta": list(fork["zeta"]), "lamda": list(fork["lamda"]),
+                      "rc": fork["cutoff_ang"], "elements": list(fork["elements"]), "multiplicity": fork["multiplicity"]},
+        "normalize_kwargs": {},
+        "mlp_kwargs": {"units": list(fork["hidden"]) + [1], "num_relations": fork["max_elements"],
+                       "activation": list(fork["hidden_activation"]) + ["linear"]},
+        "node_pooling_args": {"pooling_method": "sum"},
+        "output_embedding": "graph", "output_to_tensor": True, "use_output_mlp": False,
+    }
+
+
+def angle_indices(idx, edge_pairing="kj"):
+    """Angle triples ``(i, j, k)`` of one molecule's edge list: a NumPy restatement of kgcnn/graph/adj.py::
+    get_angle_indices with SetAngle's defaults (no multi, self or reverse edges).  For edge ``n = (i, j)`` the partner
+    edges ``m`` are those whose fixed end (``edge_pairing``: "kj" - column 1, "ik" - column 0) equals the edge's
+    (column 1 for "kj", column 0 for "ik"); the triple is ``(i, j, idx[m, k-position])``; order: by n, then m."""
+    idx = np.asarray(idx, dtype=np.int64).reshape(-1, 2)
+    if len(idx) == 0:
+        return np.zeros((0, 3), np.int64)
+    pos_k = 0 if edge_pairing[0] == "k" else 1
+    pos_fix = 1 if edge_pairing[0] == "k" else 0
+    pos_ij = 0 if "i" in edge_pairing else 1
+    a, b = idx[:, None, :], idx[None, :, :]
+    mask = b[..., pos_fix] == a[..., pos_ij]
+    mask &= (b[..., 0] != a[..., 0]) | (b[..., 1] != a[..., 1])      # multi edges
+    mask &= (b[..., 0] != a[..., 1]) | (b[..., 1] != a[..., 0])      # reverse edges
+    np.fill_diagonal(mask, False)                                    # self
+    n, m = np.nonzero(mask)
+    return np.concatenate([idx[n], idx[m, pos_k][:, None]], axis=-1).astype(np.int64)
+
+
+def hdnnp_batch(num_graphs=128, seed=3456, sigma=1.5, min_distance=0.9, z=ALANINE_DIPEPTIDE_Z, fork=HDNNP_FORK,
+                edge_pairing="kj"):
+    """Alanine-dipeptide-shaped molecules for HDNNP2nd: 22 atoms (H/C/N/O), coordinates ``N(0, sigma^2)`` in Angstrom
+    redrawn per atom until every pair is at least ``min_distance`` apart, stored in Bohr.  Range indices by the fork's
+    radius, ``cutoff_rad`` + 1 Angstrom in Bohr (all pairs within it, no neighbour limit); angle indices by
+    :func:`angle_indices`."""
+    rng = np.random.default_rng(seed)
+    radius = fork["cutoff_rad"] + BOHR_PER_ANGSTROM
+    zs, xs, es, ts = [], [], [], []
+    for _ in range(num_graphs):
+        xyz = np.zeros((len(z), 3))
+        for a in range(len(z)):
+            while True:
+                p = rng.normal(0.0, sigma, size=3)
+                if a == 0 or np.min(np.linalg.norm(xyz[:a] - p, axis=-1)) >= min_distance:
+                    break
+            xyz[a] = p
+        xyz = (xyz * BOHR_PER_ANGSTROM).astype(np.float32)
+        ei = radius_graph(xyz, max_distance=radius, max_neighbours=None)
+        zs.append(np.asarray(z, np.int64)); xs.append(xyz); es.append(ei); ts.append(angle_indices(ei, edge_pairing))
+    return {
+        "node_number": np.concatenate(zs), "node_coordinates": np.concatenate(xs, axis=0),
+        "edge_indices": np.concatenate(es, axis=0).reshape(-1, 2).astype(np.int64),
+        "angle_indices": np.concatenate(ts, axis=0).reshape(-1, 3).astype(np.int64),
+        "node_splits": _splits([len(x) for x in xs]), "edge_splits": _splits([len(e) for e in es]),
+        "angle_splits": _splits([len(t) for t in ts]),
+    }
+
+
+def hdnnp_params(seed=10, fork=HDNNP_FORK, random_bias=True):
+    """Random RelationalMLP weights of the fork's HDNNP2nd in ``model.weights`` order: per layer ``kernel``
+    ``(max_elements, in, units)`` (Glorot per relation) and ``bias``; ``in`` = 140 radial + 500 angular functions."""
+    rng = np.random.default_rng(seed)
+    n_el = len(fork["elements"])
+    fan = len(fork["rs"]) * len(fork["eta"]) * n_el + \
+        len(fork["eta_ang"]) * len(fork["zeta"]) * len(fork["lamda"]) * (n_el * (n_el + 1) // 2)
+    p = {}
+    for k, u in enumerate(list(fork["hidden"]) + [1]):
+        p["mlp/%d/kernel" % k] = glorot_uniform(rng, fan, u, shape=(fork["max_elements"], fan, u))
+        p["mlp/%d/bias" % k] = (rng.uniform(-0.1, 0.1, size=u).astype(np.float32) if random_bias
+                                else np.zeros(u, np.float32))
+        fan = u
+    return p
