@@ -17,6 +17,7 @@ MP_OK, MP_EINVAL, MP_EINDEX, MP_EHIP, MP_ENOTSUP = 0, -1, -2, -3, -4
 MP_SUM, MP_MEAN, MP_MAX, MP_MIN = 0, 1, 2, 3
 MP_ADD, MP_SUB, MP_MUL = 0, 1, 2
 MP_PAINN_FILTER_IMAGE_BYTES = 73728   # include/mpengine.h
+MP_CENT_MAX_ATOMS = 128               # include/mpengine.h: atoms per molecule of the charge solve
 MP_FLAG_OOB, MP_FLAG_UNSORTED_COL0, MP_FLAG_UNSORTED_COL1 = 1, 2, 4
 
 ACTIVATION_CODES = {
@@ -160,6 +161,10 @@ _SIGNATURES = {
     "mp_relational_dense_f32": [P, c_int64, c_int64, P, c_int64, P, P, c_int64, c_int, c_float, c_int, P, P, P, P],
     "mp_relational_dense_wgrad_ws_bytes": [c_int64, c_int64, P],
     "mp_relational_dense_wgrad_f32": [P, c_int64, c_int64, P, c_int64, P, c_int64, P, P, P, c_size_t, P],
+    "mp_cent_charge_f32": [P, P, P, c_int64, c_int64, P, P, P, P, c_int, P, P],
+    "mp_cent_charge_grad_f32": [P, P, P, c_int64, c_int64, P, P, P, P, c_int, P, P, P],
+    "mp_gauss_energy_f32": [P, P, P, P, c_int64, c_int64, P, c_int64, P, P, c_int, c_float, P, P],
+    "mp_gauss_energy_grad_f32": [P, P, P, P, c_int64, c_int64, P, c_int64, P, P, P, P, P, c_int, c_float, P, P, P, P],
 }
 _RESTYPES = {"mp_last_error": c_char_p}
 

@@ -894,3 +894,78 @@ class RelationalDenseAdjoint(torch.autograd.Function):
         if not need_b:
             b_bar = None
         return g_bar, x_bar, w_bar, b_bar, None, None, None, None, None, None, None
+
+
+# ------------------------------------------------------------------------------------------------ HDNNP4th
+class RaggedToPadded(torch.autograd.Function):
+    """Ragged values (N, F) -> zero-padded (G, Nmax, F) (``mp_ragged_to_padded_f32``, the kernel of ``ChangeTensorType``),
+    for an output that a loss reaches (HDNNP4th's padded charges).  Backward: the real rows of the upstream gradient,
+    gathered by ``mp_gather_rows_f32``."""
+
+    @staticmethod
+    def forward(ctx, values, row_splits, splits_host):
+        counts = splits_host[1:] - splits_host[:-1]
+        g, nmax = int(counts.size), int(counts.max()) if counts.size else 0
+        vals = values.contiguous()
+        width = vals.numel() // max(int(vals.shape[0]), 1)
+        padded = torch.empty((g, nmax) + tuple(vals.shape[1:]), dtype=torch.float32, device=vals.device)
+        _ffi.call("mp_ragged_to_padded_f32", _ffi.ptr(vals), _ffi.ptr(row_splits), g, nmax, max(width, 1),
+                  _ffi.ptr(padded), None, _ffi.stream())
+        ctx.splits_host, ctx.nmax, ctx.width, ctx.shape = splits_host, nmax, max(width, 1), tuple(vals.shape)
+        return padded
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        import numpy as np
+        s = ctx.splits_host
+        counts = s[1:] - s[:-1]
+        n = int(s[-1])
+        graph = np.repeat(np.arange(counts.size, dtype=np.int64), counts)
+        rows = (graph * ctx.nmax + np.arange(n, dtype=np.int64) - s[:-1][graph]).astype(np.int32)
+        idx = torch.from_numpy(rows).to(g.device)
+        out = torch.empty(ctx.shape, dtype=torch.float32, device=g.device)
+        if n:
+            _ffi.call("mp_gather_rows_f32", _ffi.ptr(g.contiguous()), int(counts.size) * ctx.nmax, ctx.width,
+                      _ffi.ptr(idx), n, 1, _ffi.int32_array([0]), _ffi.ptr(out), _ffi.stream())
+        return out, None, None
+
+
+class CentCharge(torch.autograd.Function):
+    """CENT charges Q (N, 1) of electronegativities chi (N,) and coordinates (N, 3) on csrc/mp_cent.hip; ``spec``
+    (layers/conv/hdnnp_conv.py) holds the atomic numbers, molecule splits, total charges and tables.  Backward:
+    ``mp_cent_charge_grad_f32`` (chi_bar = w, x_bar), each only when asked.  It is first order only: a backward in grad
+    mode - the ``create_graph`` pass of a force loss - raises ``NotImplementedError``."""
+
+    @staticmethod
+    def forward(ctx, chi, xyz, spec):
+        q = spec.forward(chi, xyz)
+        ctx.spec, ctx.xyz, ctx.q = spec, xyz.detach(), q.detach()
+        return q
+
+    @staticmethod
+    def backward(ctx, g):
+        if torch.is_grad_enabled():
+            raise NotImplementedError("second derivative of the charge equilibration (CENTCharge: a force loss or a "
+                                      "create_graph backward through the charge solve) is not implemented")
+        chi_bar, x_bar = ctx.spec.grad(ctx.xyz, ctx.q, g, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        return chi_bar, x_bar, None
+
+
+class GaussElectrostatics(torch.autograd.Function):
+    """Electrostatic energy (G, 1) of Gaussian charges q (N,) at coordinates (N, 3) over the range indices
+    (``mp_gauss_energy_f32``).  Backward: ``mp_gauss_energy_grad_f32`` (q_bar, x_bar), each only when asked; first order
+    only, like ``CentCharge``."""
+
+    @staticmethod
+    def forward(ctx, q, xyz, spec):
+        ctx.spec, ctx.q, ctx.xyz = spec, q.detach(), xyz.detach()
+        return spec.forward(q, xyz)
+
+    @staticmethod
+    def backward(ctx, g):
+        if torch.is_grad_enabled():
+            raise NotImplementedError("second derivative of the charge equilibration's electrostatic energy "
+                                      "(ElectrostaticEnergyGaussCharge) is not implemented")
+        q_bar, x_bar = ctx.spec.grad(ctx.q, ctx.xyz, g, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        return q_bar, x_bar, None

@@ -26,16 +26,46 @@ def _reduce(per_sample, sample_weight):
     return per_sample.mean()
 
 
-def mean_absolute_error(y_pred, y_true, sample_weight=None):
+def _real_rows(p, y_true):
+    """A ragged per-atom target ``(B, [N], ...)`` against a padded prediction ``(B, Nmax, ...)`` whose element count
+    differs from the target's (molecules of different sizes: the reshape below cannot pair them): the prediction's rows
+    of the real atoms, by the target's row splits, and the target's values.  ``None`` for every other pair, which keeps
+    the reshape (for molecules of one size it already pairs atom with atom)."""
+    if not isinstance(y_true, RaggedTensor) or not torch.is_tensor(p):
+        return None
+    t = y_true.values
+    if p.dim() != t.dim() + 1 or int(p.shape[0]) != y_true.nrows() or t.numel() == p.numel():
+        return None
+    splits = np.asarray(y_true.row_splits_host(), dtype=np.int64)
+    counts = splits[1:] - splits[:-1]
+    if tuple(p.shape[2:]) != tuple(t.shape[1:]) or (counts.size and int(counts.max()) > int(p.shape[1])):
+        return None
+    graph = np.repeat(np.arange(counts.size, dtype=np.int64), counts)
+    local = np.arange(int(splits[-1]), dtype=np.int64) - splits[:-1][graph]
+    rows = p[torch.from_numpy(graph).to(p.device), torch.from_numpy(local).to(p.device)]
+    return rows, t.to(device=p.device, dtype=p.dtype)
+
+
+def _per_sample(y_pred, y_true, sample_weight, term):
     p = _values(y_pred)
+    real = _real_rows(p, y_true)
+    if real is not None:
+        # the mean runs over the real atoms of the batch, as the force loss does (flat_target)
+        if sample_weight is not None:
+            raise NotImplementedError("sample_weight with a ragged target against a padded prediction is not "
+                                      "implemented")
+        rows, t = real
+        return term(rows - t).reshape(int(t.shape[0]), -1).mean(dim=-1).mean()
     t = _values(y_true, p).to(p.dtype)
-    return _reduce((p - t.reshape(p.shape)).abs().mean(dim=-1), sample_weight)
+    return _reduce(term(p - t.reshape(p.shape)).mean(dim=-1), sample_weight)
+
+
+def mean_absolute_error(y_pred, y_true, sample_weight=None):
+    return _per_sample(y_pred, y_true, sample_weight, torch.abs)
 
 
 def mean_squared_error(y_pred, y_true, sample_weight=None):
-    p = _values(y_pred)
-    t = _values(y_true, p).to(p.dtype)
-    return _reduce((p - t.reshape(p.shape)).square().mean(dim=-1), sample_weight)
+    return _per_sample(y_pred, y_true, sample_weight, torch.square)
 
 
 def categorical_crossentropy(y_pred, y_true, sample_weight=None):

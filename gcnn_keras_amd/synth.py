@@ -342,3 +342,108 @@ def hdnnp_params(seed=10, fork=HDNNP_FORK, random_bias=True):
                                 else np.zeros(u, np.float32))
         fan = u
     return p
+
+
+# ---------------------------------------------------------------------------------------------------------- HDNNP4th
+# The fork's HDNNP4th table (force_hdnnp4th.py:41-71, charge_hdnnp4th.py): the HDNNP2nd symmetry functions, a [15] tanh
+# charge network and the [35, 35] tanh local network.
+HDNNP4TH_FORK = dict(HDNNP_FORK, charge_hidden=[15], charge_hidden_activation=["tanh"])
+MIXED_SIZES = (1, 2, 3, 22, 128)   # the molecule sizes of hdnnp4th_batch(mixed=True); 128 = the charge solve's bound
+
+
+def hdnnp4th_model_kwargs(fork=HDNNP4TH_FORK, output_embedding="charge+qm_energy"):
+    """``HDNNP4th.make_model_behler`` keyword arguments of the fork's force_hdnnp4th.py:151-198 (custom tanh as "tanh")."""
+    kw = hdnnp_model_kwargs(fork)
+    local = kw.pop("mlp_kwargs")
+    kw.update({
+        "mlp_charge_kwargs": {"units": list(fork["charge_hidden"]) + [1], "num_relations": fork["max_elements"],
+                              "activation": list(fork["charge_hidden_activation"]) + ["linear"]},
+        "mlp_local_kwargs": local,
+        "cent_kwargs": {},
+        "electrostatic_kwargs": {"name": "electrostatic_layer", "use_physical_params": True, "param_trainable": False},
+        "qmmm_kwargs": {"name": "qmmm_layer"},
+        "output_embedding": output_embedding,
+    })
+    return kw
+
+
+def hdnnp4th_params(seed=12, fork=HDNNP4TH_FORK, random_bias=True):
+    """Random weights of the fork's two RelationalMLPs in ``model.weights`` order: the charge network on 640 + 1 inputs
+    (symmetry functions and esp), then the local network on 640 + 2 (and the charge)."""
+    rng = np.random.default_rng(seed)
+    n_el = len(fork["elements"])
+    width = len(fork["rs"]) * len(fork["eta"]) * n_el + \
+        len(fork["eta_ang"]) * len(fork["zeta"]) * len(fork["lamda"]) * (n_el * (n_el + 1) // 2)
+    p = {}
+    for net, fan, hidden in (("mlp_charge", width + 1, fork["charge_hidden"]), ("mlp_local", width + 2, fork["hidden"])):
+        for k, u in enumerate(list(hidden) + [1]):
+            p["%s/%d/kernel" % (net, k)] = glorot_uniform(rng, fan, u, shape=(fork["max_elements"], fan, u))
+            p["%s/%d/bias" % (net, k)] = (rng.uniform(-0.1, 0.1, size=u).astype(np.float32) if random_bias
+                                          else np.zeros(u, np.float32))
+            fan = u
+    return p
+
+
+def _molecule(rng, n, sigma, min_distance):
+    """``n`` positions ``N(0, sigma^2)`` in Angstrom, each redrawn until it is ``min_distance`` from the earlier ones."""
+    xyz = np.zeros((n, 3))
+    for a in range(n):
+        while True:
+            p = rng.normal(0.0, sigma, size=3)
+            if a == 0 or np.min(np.linalg.norm(xyz[:a] - p, axis=-1)) >= min_distance:
+                break
+        xyz[a] = p
+    return xyz
+
+
+def hdnnp4th_batch(num_graphs=128, seed=4567, sigma=1.5, min_distance=0.9, mixed=False, angles=None, num_mm=12,
+                   shell=4.0, fork=HDNNP4TH_FORK, edge_pairing="kj"):
+    """HDNNP4th inputs: :func:`hdnnp_batch`'s alanine-dipeptide-shaped molecules (22 atoms, Bohr, range indices by the
+    fork's radius, angle indices) plus
+
+    * ``total_charge`` ``(G, 1)`` in {-1, 0, 1};
+    * ``num_mm`` MM point charges per molecule, uniform in [-1, 1], on a shell ``shell`` Angstrom outside the molecule's
+      farthest atom from its centroid (``mm_positions`` ``(G, num_mm, 3)`` Bohr, ``mm_charges`` ``(G, num_mm)``);
+    * ``esp_i = sum_m q_m / |x_i - R_m|`` ``(N,)`` and its gradient ``esp_grad_i = -sum_m q_m (x_i - R_m) / |x_i - R_m|^3``
+      ``(N, 3)``, computed in float64 and stored float32.
+
+    ``mixed=True`` cycles the molecule sizes through :data:`MIXED_SIZES` (elements H/C/N/O drawn at random, alanine's
+    for 22 atoms) with the spread ``sigma`` scaled by the cube root of the atom count, so that the rejection sampling
+    keeps its density and ends.  Angle indices (``angles``, default: not for mixed batches) build an M x M mask per
+    molecule and grow cubically with its size: the large molecules serve the charge solve and the electrostatics."""
+    rng = np.random.default_rng(seed)
+    if angles is None:
+        angles = not mixed
+    radius = fork["cutoff_rad"] + BOHR_PER_ANGSTROM
+    zs, xs, es, ts, qt, mm_x, mm_q, esp, esp_grad = [], [], [], [], [], [], [], [], []
+    for g in range(num_graphs):
+        n = MIXED_SIZES[g % len(MIXED_SIZES)] if mixed else len(ALANINE_DIPEPTIDE_Z)
+        z = ALANINE_DIPEPTIDE_Z if n == len(ALANINE_DIPEPTIDE_Z) else \
+            rng.choice(np.array(fork["elements"], np.int64), size=n)
+        xyz = _molecule(rng, n, sigma * max(1.0, (n / 22.0) ** (1.0 / 3.0)), min_distance)
+        centre = xyz.mean(axis=0)
+        r_out = float(np.max(np.linalg.norm(xyz - centre, axis=-1))) + shell
+        d = rng.normal(size=(num_mm, 3))
+        pos = centre + r_out * d / np.linalg.norm(d, axis=-1, keepdims=True)
+        chg = rng.uniform(-1.0, 1.0, size=num_mm)
+        xb = (xyz * BOHR_PER_ANGSTROM).astype(np.float32)
+        pb = pos * BOHR_PER_ANGSTROM
+        diff = xb.astype(np.float64)[:, None, :] - pb[None, :, :]          # (n, m, 3) Bohr
+        dist = np.linalg.norm(diff, axis=-1)
+        esp.append((chg[None, :] / dist).sum(axis=1).astype(np.float32))
+        esp_grad.append((-(chg[None, :, None] * diff) / dist[..., None] ** 3).sum(axis=1).astype(np.float32))
+        ei = radius_graph(xb, max_distance=radius, max_neighbours=None)
+        zs.append(np.asarray(z, np.int64)); xs.append(xb); es.append(ei)
+        ts.append(angle_indices(ei, edge_pairing) if angles else np.zeros((0, 3), np.int64))
+        qt.append(float(rng.integers(-1, 2)))
+        mm_x.append(pb.astype(np.float32)); mm_q.append(chg.astype(np.float32))
+    return {
+        "node_number": np.concatenate(zs), "node_coordinates": np.concatenate(xs, axis=0),
+        "edge_indices": np.concatenate(es, axis=0).reshape(-1, 2).astype(np.int64),
+        "angle_indices": np.concatenate(ts, axis=0).reshape(-1, 3).astype(np.int64),
+        "node_splits": _splits([len(x) for x in xs]), "edge_splits": _splits([len(e) for e in es]),
+        "angle_splits": _splits([len(t) for t in ts]),
+        "total_charge": np.array(qt, np.float32).reshape(-1, 1),
+        "esp": np.concatenate(esp), "esp_grad": np.concatenate(esp_grad, axis=0),
+        "mm_positions": np.stack(mm_x), "mm_charges": np.stack(mm_q),
+    }

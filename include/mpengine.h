@@ -747,6 +747,43 @@ int mp_relational_dense_wgrad_f32(const float* x, int64_t R, int64_t K, const in
                                   const float* g, int64_t U, float* dW, float* db, void* ws, size_t ws_bytes,
                                   mpStream_t stream);
 
+/* ---------------------------------------------------------------- HDNNP4th: charge equilibration ---------- */
+/* CENT charges and Gaussian-charge electrostatics (csrc/mp_cent.hip), Ko et al.'s fourth-generation HDNNP
+ * (kgcnn/literature/HDNNP4th.py:25-189).  xyz (N,3); z (N) int64 atomic numbers; node_splits (G+1) int64 row splits of
+ * the molecules; sigma / hardness: per-atomic-number tables of ntab entries (the reference's 97, Z = 0..96); an atomic
+ * number outside [0, ntab) reads 0 (the reference's out-of-range gather on a GPU).
+ *
+ * mp_cent_charge_f32: hdnnp_conv.py:148-258, per molecule the bordered system [[A, 1], [1^T, 0]] [Q; lambda] =
+ *   [chi; Qtot] over ALL atom pairs of the molecule: A_ii = J[z_i] + 1 / (sigma_i sqrt(pi)), A_ij = erf(r_ij / (sqrt(2)
+ *   gamma_ij)) / r_ij with gamma_ij = sqrt(sigma_i^2 + sigma_j^2) (0 where divide_no_nan gives 0); right-hand side +chi
+ *   as the reference.  qtot (G).  One wave per molecule, the matrix in LDS, Cholesky + Schur complement in FP64.  At most
+ *   MP_CENT_MAX_ATOMS atoms per molecule (the caller rejects larger ones; the kernel writes NaN for them), a molecule
+ *   whose factorisation meets a non-positive pivot gets NaN charges, a 0-atom molecule produces nothing.
+ * mp_cent_charge_grad_f32: its reverse for an upstream gQ (N), given the forward's charges q: w = A^-1 gQ - mu A^-1 1,
+ *   mu = 1^T A^-1 gQ / 1^T A^-1 1; chi_bar = w, x_bar_i = -sum_{j != i} (w_i Q_j + w_j Q_i) f'(r_ij) (x_i - x_j) / r_ij.
+ *   Refactors A (no workspace); either output nullable.
+ * mp_gauss_energy_f32: hdnnp_conv.py:391-428, energy (G) = sum over the molecule's range_indices (cols = the index plan's
+ *   shifted int32 columns (2, M), edge_splits (G+1)) of q_i q_j f(r_ij) / multiplicity (no division when it is 0) + sum
+ *   over its atoms of divide_no_nan(q_i^2, sigma_i) / (2 sqrt(pi)).
+ * mp_gauss_energy_grad_f32: its reverse for an upstream g_energy (G): q_bar (N), x_bar (N,3), per atom over the CSR
+ *   (ptrc / permc, permc nullable when column c is sorted) of both index columns in list order; either output nullable.
+ * Deterministic (fixed per-molecule reduction order, no float atomics); N = 0 or G = 0 needs no device. */
+#define MP_CENT_MAX_ATOMS 128
+int mp_cent_charge_f32(const float* xyz, const int64_t* z, const int64_t* node_splits, int64_t G, int64_t N,
+                       const float* chi, const float* qtot, const float* sigma, const float* hardness, int ntab,
+                       float* q, mpStream_t stream);
+int mp_cent_charge_grad_f32(const float* xyz, const int64_t* z, const int64_t* node_splits, int64_t G, int64_t N,
+                            const float* q, const float* gq, const float* sigma, const float* hardness, int ntab,
+                            float* chi_bar, float* x_bar, mpStream_t stream);
+int mp_gauss_energy_f32(const float* xyz, const int64_t* z, const float* q, const int64_t* node_splits, int64_t G,
+                        int64_t N, const int32_t* cols, int64_t M, const int64_t* edge_splits, const float* sigma,
+                        int ntab, float multiplicity, float* energy, mpStream_t stream);
+int mp_gauss_energy_grad_f32(const float* xyz, const int64_t* z, const float* q, const int64_t* node_splits, int64_t G,
+                             int64_t N, const int32_t* cols, int64_t M, const int32_t* ptr0, const int32_t* perm0,
+                             const int32_t* ptr1, const int32_t* perm1, const float* sigma, int ntab,
+                             float multiplicity, const float* g_energy, float* q_bar, float* x_bar,
+                             mpStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,289 @@
+"""HDNNP4th without a GPU: the charge-equilibration entry points are declared, bound and validate their arguments; the
+tables equal the reference layers' defaults (tests/golden/cent_reference_tables.npz); config keys, builder contracts and
+the guards; self-checks of the torch restatement (tests/hdnnp4th_reference.py) in float64; the loss on ragged charge
+targets against padded predictions.  No kernel is launched."""
+import ctypes
+import math
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import hdnnp4th_reference as ref
+from gcnn_keras_amd import _ffi, synth
+from gcnn_keras_amd.layers.conv.hdnnp_conv import (CENTCharge, CENTChargePlusElectrostaticEnergy,
+                                                   ElectrostaticEnergyGaussCharge, ElectrostaticQMMMEnergyPointCharge,
+                                                   ElectrostaticQMMMForcePointCharge)
+from gcnn_keras_amd.literature import HDNNP4th
+from gcnn_keras_amd.model.losses import mean_absolute_error, mean_squared_error
+from gcnn_keras_amd.ragged import RaggedTensor
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW_SYMBOLS = ("mp_cent_charge_f32", "mp_cent_charge_grad_f32", "mp_gauss_energy_f32", "mp_gauss_energy_grad_f32")
+
+
+def test_new_symbols_in_header_and_ctypes_table():
+    raw = open(os.path.join(ROOT, "include", "mpengine.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
+    lib = _ffi.lib()
+    for name in NEW_SYMBOLS:
+        assert re.search(r"\b%s\s*\(" % name, text), name
+        assert name in _ffi.declared_symbols(), name
+        assert hasattr(lib, name), name
+    for cite in ("hdnnp_conv.py:148-258", "hdnnp_conv.py:391-428", "HDNNP4th.py:25-189"):
+        assert cite in raw, cite
+    assert "#define MP_CENT_MAX_ATOMS %d" % _ffi.MP_CENT_MAX_ATOMS in raw and _ffi.MP_CENT_MAX_ATOMS >= 128
+
+
+def test_argument_errors_and_zero_sized_calls():
+    lib = _ffi.lib()
+    host = (ctypes.c_float * 4)()
+    buf = ctypes.cast(host, ctypes.c_void_p)
+    assert lib.mp_cent_charge_f32(None, None, None, -1, 0, None, None, buf, buf, 97, None, None) == _ffi.MP_EINVAL
+    assert b"mp_cent_charge_f32" in lib.mp_last_error()
+    assert lib.mp_cent_charge_f32(buf, buf, buf, 2, 4, buf, buf, buf, buf, 0, buf, None) == _ffi.MP_EINVAL
+    assert lib.mp_cent_charge_f32(buf, buf, buf, 2, 4, None, buf, buf, buf, 97, buf, None) == _ffi.MP_EINVAL
+    assert lib.mp_cent_charge_grad_f32(buf, buf, buf, 2, 4, buf, None, buf, buf, 97, buf, None, None) == \
+        _ffi.MP_EINVAL
+    assert lib.mp_gauss_energy_f32(buf, buf, buf, buf, 2, 4, None, 3, buf, buf, 97, 2.0, buf, None) == _ffi.MP_EINVAL
+    assert lib.mp_gauss_energy_grad_f32(buf, buf, buf, buf, 2, 4, buf, 3, None, None, buf, None, buf, 97, 2.0, buf,
+                                        buf, None, None) == _ffi.MP_EINVAL
+    with pytest.raises(ValueError):
+        _ffi.check(lib.mp_gauss_energy_f32(None, None, None, None, -2, 0, None, 0, None, None, 97, 0.0, None, None))
+    # zero-sized problems, and a reverse that asks for nothing, need no device
+    assert lib.mp_cent_charge_f32(None, None, None, 0, 0, None, None, buf, buf, 97, None, None) == _ffi.MP_OK
+    assert lib.mp_cent_charge_grad_f32(buf, buf, buf, 2, 4, buf, buf, buf, buf, 97, None, None, None) == _ffi.MP_OK
+    assert lib.mp_gauss_energy_f32(None, None, None, None, 0, 0, None, 0, None, buf, 97, 2.0, None, None) == _ffi.MP_OK
+    assert lib.mp_gauss_energy_grad_f32(None, None, None, None, 0, 0, None, 0, None, None, None, None, buf, 97, 2.0,
+                                        None, None, None, None) == _ffi.MP_OK
+
+
+def test_tables_equal_the_reference_defaults(golden_dir):
+    d = np.load(os.path.join(golden_dir, "cent_reference_tables.npz"))
+    cent, gauss, combined = CENTCharge(), ElectrostaticEnergyGaussCharge(), CENTChargePlusElectrostaticEnergy()
+    for t in (cent.weight_sigma, cent.weight_j, gauss.weight_sigma):
+        assert t.dtype == np.float32 and t.shape == (97,)
+    assert np.array_equal(cent.weight_sigma, d["cent_sigma_bohr"].astype(np.float32))
+    assert np.array_equal(cent.weight_j, d["cent_hardness"].astype(np.float32))
+    assert np.array_equal(gauss.weight_sigma, d["gauss_sigma_angstrom"].astype(np.float32))
+    # the combined layer's energy uses CENT's table (Bohr), as the reference's suppressed initialisation does
+    assert np.array_equal(combined.weight_sigma, d["cent_sigma_bohr"].astype(np.float32))
+    assert np.array_equal(combined.weight_j, d["cent_hardness"].astype(np.float32))
+    assert CENTCharge._max_atomic_number == 97 and ElectrostaticEnergyGaussCharge._max_atomic_number == 97
+    assert cent.weights == [] and combined.weights == []
+
+
+def test_get_config_keys():
+    params = {"use_physical_params", "param_constraint", "param_regularizer", "param_initializer", "param_trainable"}
+    assert {"output_to_tensor", "name"} | params <= set(CENTCharge().get_config())
+    assert {"add_eps", "multiplicity", "_suppress_weight_initialization"} | params <= \
+        set(ElectrostaticEnergyGaussCharge().get_config())
+    assert {"add_eps", "multiplicity", "output_to_tensor"} | params <= \
+        set(CENTChargePlusElectrostaticEnergy().get_config())
+    assert "add_eps" in ElectrostaticQMMMEnergyPointCharge().get_config()
+    assert "name" in ElectrostaticQMMMForcePointCharge().get_config()
+    assert ElectrostaticEnergyGaussCharge(multiplicity=None).get_config()["multiplicity"] is None
+
+
+def test_unsupported_options_raise():
+    for cls in (CENTCharge, ElectrostaticEnergyGaussCharge, CENTChargePlusElectrostaticEnergy):
+        with pytest.raises(NotImplementedError):
+            cls(param_trainable=True)
+        with pytest.raises(NotImplementedError):
+            cls(use_physical_params=False)
+    for cls in (ElectrostaticEnergyGaussCharge, CENTChargePlusElectrostaticEnergy):
+        with pytest.raises(NotImplementedError):
+            cls(add_eps=True)
+    with pytest.raises(NotImplementedError):
+        CENTCharge(output_to_tensor=True)
+    with pytest.raises(NotImplementedError):
+        HDNNP4th.make_model_behler(**dict(synth.hdnnp4th_model_kwargs(), normalize_kwargs={"epsilon": 1e-3}))
+    with pytest.raises(NotImplementedError):
+        HDNNP4th.make_model_behler_charge_separat(**dict(synth.hdnnp4th_model_kwargs(), normalize_kwargs={"x": 1}))
+
+
+def test_builder_defaults_and_contracts():
+    assert HDNNP4th.__model_version__ == "2023.02.17"
+    d = HDNNP4th.model_default_behler
+    assert [i["name"] for i in d["inputs"]] == ["node_number", "node_coordinates", "range_indices",
+                                                "angle_indices_nodes", "total_charge", "esp", "esp_grad"]
+    assert d["electrostatic_kwargs"] == {"name": "electrostatic_layer", "use_physical_params": True,
+                                         "param_trainable": False}
+    assert {"cent_kwargs", "qmmm_kwargs", "mlp_charge_kwargs", "mlp_local_kwargs", "energy_mean_and_var"} <= set(d)
+    with pytest.raises(ValueError):
+        HDNNP4th.make_model_behler(unknown_key=1)
+    kw = synth.hdnnp4th_model_kwargs()
+    with pytest.raises(ValueError, match="HDNNP4th"):
+        HDNNP4th.make_model_behler(**dict(kw, output_embedding="node"))
+    bad = dict(kw, mlp_local_kwargs=dict(kw["mlp_local_kwargs"], num_relations=8))
+    with pytest.raises(AssertionError, match="mlp_local_kwargs"):
+        HDNNP4th.make_model_behler(**bad)
+    # the elemental_mapping -> elements fallback of HDNNP2nd._mapping
+    mapped = dict(kw, g2_kwargs=dict(kw["g2_kwargs"], elemental_mapping=[1, 6, 7, 40]))
+    with pytest.raises(AssertionError, match="g2_kwargs"):
+        HDNNP4th.make_model_behler(**mapped)
+    charge_shapes = [(30, 641, 15), (15,), (30, 15, 1), (1,)]
+    local_shapes = [(30, 642, 35), (35,), (30, 35, 35), (35,), (30, 35, 1), (1,)]
+    for emb in ("graph", "total_energy", "charge+qm_energy"):
+        m = HDNNP4th.make_model_behler(**dict(kw, output_embedding=emb))
+        assert [tuple(t.shape) for _, t in m.weights] == charge_shapes + local_shapes
+        assert m.auto_graph is True and m.__kgcnn_model_version__ == "2023.02.17"
+    for emb in ("charge", "electrostatic_energy"):
+        m = HDNNP4th.make_model_behler(**dict(kw, output_embedding=emb))
+        assert [tuple(t.shape) for _, t in m.weights] == charge_shapes
+    assert [v.shape for v in synth.hdnnp4th_params().values()] == charge_shapes + local_shapes
+    mc, me = HDNNP4th.make_model_behler_charge_separat(**dict(kw, output_embedding="graph"))
+    assert [tuple(t.shape) for _, t in mc.weights] == charge_shapes
+    assert [tuple(t.shape) for _, t in me.weights] == charge_shapes + local_shapes
+    assert all(a is b for (_, a), (_, b) in zip(mc.weights, me.weights))       # shared layers
+    g2 = {k: kw["g2_kwargs"][k] for k in ("eta", "rs", "rc", "elements")}
+    rep = HDNNP4th.make_model_rep(g2_kwargs=g2, g4_kwargs=kw["g4_kwargs"])
+    assert rep.weights == []
+    inputs = list(HDNNP4th.model_default_behler["inputs"][:5]) + [
+        {"shape": (None, 640), "name": "rep", "dtype": "float32", "ragged": True},
+        {"shape": (None,), "name": "esp", "dtype": "float32", "ragged": True}]
+    learn = HDNNP4th.make_model_learn(inputs=inputs, mlp_charge_kwargs=kw["mlp_charge_kwargs"],
+                                      mlp_local_kwargs=kw["mlp_local_kwargs"], output_embedding="graph")
+    assert [tuple(t.shape) for _, t in learn.weights] == charge_shapes + local_shapes
+    with pytest.raises(ValueError):
+        HDNNP4th.make_model_learn(inputs=inputs, mlp_charge_kwargs=kw["mlp_charge_kwargs"],
+                                  mlp_local_kwargs=kw["mlp_local_kwargs"], output_embedding="charge")
+
+
+def test_fork_configuration():
+    kw = synth.hdnnp4th_model_kwargs()
+    assert kw["mlp_charge_kwargs"] == {"units": [15, 1], "num_relations": 30, "activation": ["tanh", "linear"]}
+    assert kw["mlp_local_kwargs"] == {"units": [35, 35, 1], "num_relations": 30, "activation": ["tanh", "tanh", "linear"]}
+    assert kw["output_embedding"] == "charge+qm_energy" and kw["g4_kwargs"]["multiplicity"] == 2.0
+    assert kw["g2_kwargs"]["elements"] == [1, 6, 7, 8]
+
+
+def test_synthetic_batch():
+    b = synth.hdnnp4th_batch(num_graphs=3, seed=2)
+    assert np.array_equal(np.diff(b["node_splits"]), [22, 22, 22])
+    assert set(np.unique(b["total_charge"])) <= {-1.0, 0.0, 1.0} and b["total_charge"].shape == (3, 1)
+    assert b["esp"].shape == (66,) and b["esp_grad"].shape == (66, 3) and b["esp"].dtype == np.float32
+    # esp and its gradient from the MM charges, and the gradient is the derivative of esp
+    x = b["node_coordinates"].astype(np.float64)
+    for g in range(3):
+        lo = b["node_splits"][g]
+        d = x[lo:lo + 22, None, :] - b["mm_positions"][g][None].astype(np.float64)
+        r = np.linalg.norm(d, axis=-1)
+        assert r.min() > 1.0          # the MM charges sit outside the molecule
+        esp = (b["mm_charges"][g][None] / r).sum(1)
+        assert np.allclose(esp, b["esp"][lo:lo + 22], rtol=1e-6, atol=1e-6)
+    h = 1e-4
+    pos, q = b["mm_positions"][0].astype(np.float64), b["mm_charges"][0].astype(np.float64)
+    p0 = x[0].copy()
+    num = [((q / np.linalg.norm(p0 + h * e - pos, axis=-1)).sum() - (q / np.linalg.norm(p0 - h * e - pos, axis=-1)).sum())
+           / (2 * h) for e in np.eye(3)]
+    assert np.allclose(num, b["esp_grad"][0], rtol=1e-4, atol=1e-6)
+    m = synth.hdnnp4th_batch(num_graphs=5, seed=3, mixed=True)
+    assert np.array_equal(np.diff(m["node_splits"]), synth.MIXED_SIZES)
+    assert len(m["angle_indices"]) == 0
+
+
+# ------------------------------------------------------------------------------------------- the restatement (float64)
+_SIG = CENTCharge().weight_sigma
+_J = CENTCharge().weight_j
+D = torch.float64
+
+
+def _mol(n, seed):
+    rng = np.random.default_rng(seed)
+    z = rng.choice([1, 6, 7, 8], size=n)
+    x = rng.normal(size=(n, 3)) * 2.5
+    chi = rng.normal(size=n) * 0.3
+    return z, torch.as_tensor(x, dtype=D), torch.as_tensor(chi, dtype=D)
+
+
+def test_restatement_one_and_two_atoms():
+    z, x, chi = _mol(1, 1)
+    q = ref.cent_molecule(z, x, chi, torch.tensor(1.0, dtype=D), _SIG, _J)
+    assert abs(float(q[0]) - 1.0) < 1e-14
+    z, x, chi = _mol(2, 2)
+    qt = -1.0
+    q = ref.cent_molecule(z, x, chi, torch.tensor(qt, dtype=D), _SIG, _J).numpy()
+    s = _SIG.astype(np.float64)[z]
+    a = _J.astype(np.float64)[z] + 1.0 / s / math.sqrt(math.pi)
+    r = float(torch.linalg.norm(x[0] - x[1]))
+    f = math.erf(r / (math.sqrt(2.0) * math.sqrt(s[0] ** 2 + s[1] ** 2))) / r
+    c = chi.numpy()
+    q1 = (c[0] - c[1] + (a[1] - f) * qt) / (a[0] + a[1] - 2.0 * f)
+    assert np.allclose(q, [q1, qt - q1], rtol=1e-12, atol=1e-14)
+
+
+def test_restatement_total_charge_and_invariances():
+    z, x, chi = _mol(9, 3)
+    qt = torch.tensor(1.0, dtype=D)
+    q = ref.cent_molecule(z, x, chi, qt, _SIG, _J)
+    assert abs(float(q.sum()) - 1.0) < 1e-12
+    rot, _ = np.linalg.qr(np.random.default_rng(4).normal(size=(3, 3)))
+    xr = x @ torch.as_tensor(rot, dtype=D) + torch.tensor([1.0, -2.0, 0.5], dtype=D)
+    assert torch.allclose(ref.cent_molecule(z, xr, chi, qt, _SIG, _J), q, rtol=1e-10, atol=1e-12)
+    perm = np.random.default_rng(5).permutation(9)
+    qp = ref.cent_molecule(z[perm], x[perm], chi[perm], qt, _SIG, _J)
+    assert torch.allclose(qp, q[perm], rtol=1e-10, atol=1e-12)
+    ij = np.array([[a, b] for a in range(9) for b in range(9) if a != b])
+    ns = np.array([0, 9])
+    e = ref.gauss_energy(z, x, q, ij, ns, _SIG, 2.0)
+    er = ref.gauss_energy(z, xr, q, ij, ns, _SIG, 2.0)
+    inv = np.argsort(perm)
+    ep = ref.gauss_energy(z[perm], x[perm], q[perm], inv[ij], ns, _SIG, 2.0)
+    assert torch.allclose(e, er, rtol=1e-10) and torch.allclose(e, ep, rtol=1e-10)
+    # all pairs at multiplicity 2 = Q^T (A - diag(J)) Q / 2 (the Coulomb energy of the Gaussian densities)
+    a = torch.zeros((9, 9), dtype=D)
+    s = torch.as_tensor(_SIG.astype(np.float64)[z])
+    for i in range(9):
+        for j in range(9):
+            if i != j:
+                r = torch.linalg.norm(x[i] - x[j])
+                a[i, j] = torch.erf(r / (math.sqrt(2.0) * torch.sqrt(s[i] ** 2 + s[j] ** 2))) / r
+            else:
+                a[i, i] = 1.0 / s[i] / math.sqrt(math.pi)
+    assert torch.allclose(e.reshape(()), q @ a @ q / 2.0, rtol=1e-12)
+
+
+def test_restatement_qmmm_energy():
+    q = torch.tensor([0.5, -0.25, 1.0], dtype=D)
+    esp = torch.tensor([0.1, 0.2, -0.3], dtype=D)
+    assert torch.allclose(ref.qmmm_energy(q, esp, np.array([0, 2, 3])), torch.tensor([[0.0], [-0.3]], dtype=D))
+
+
+# ------------------------------------------------------------------------------------------- loss on ragged charges
+def _ragged_target(splits, seed=0):
+    n = int(splits[-1])
+    t = np.random.default_rng(seed).normal(size=(n, 1)).astype(np.float32)
+    return RaggedTensor(torch.as_tensor(t), torch.as_tensor(np.asarray(splits, np.int64))), t
+
+
+def _padded(values, splits, nmax, fill=0.0):
+    out = np.full((len(splits) - 1, nmax, values.shape[-1]), fill, np.float32)
+    for g in range(len(splits) - 1):
+        out[g, :splits[g + 1] - splits[g]] = values[splits[g]:splits[g + 1]]
+    return out
+
+
+@pytest.mark.parametrize("loss,term", [(mean_squared_error, np.square), (mean_absolute_error, np.abs)])
+def test_loss_ragged_target_against_padded_prediction(loss, term):
+    splits = np.array([0, 1, 3, 6, 28])
+    target, t = _ragged_target(splits, 1)
+    pred_vals = np.random.default_rng(2).normal(size=t.shape).astype(np.float32)
+    # padding holds garbage that must not count
+    pred = torch.as_tensor(_padded(pred_vals, splits, 22, fill=1e3))
+    got = float(loss(pred, target))
+    want = float(np.mean(term(pred_vals.astype(np.float64) - t)))
+    assert abs(got - want) <= 1e-6 * max(1.0, abs(want))
+    with pytest.raises(NotImplementedError):
+        loss(pred, target, sample_weight=np.ones(4))
+    # molecules of one size: the existing reshape, the same mean over the atoms
+    same = np.array([0, 5, 10])
+    target2, t2 = _ragged_target(same, 3)
+    p2 = np.random.default_rng(4).normal(size=(2, 5, 1)).astype(np.float32)
+    got2 = float(loss(torch.as_tensor(p2), target2))
+    assert abs(got2 - float(np.mean(term(p2.reshape(-1, 1).astype(np.float64) - t2)))) <= 1e-6
+    # every pair that worked before gives what it gave before
+    flat = torch.as_tensor(pred_vals)
+    assert float(loss(flat, target)) == float(loss(flat, torch.as_tensor(t)))
