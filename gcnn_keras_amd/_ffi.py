@@ -18,12 +18,13 @@ MP_SUM, MP_MEAN, MP_MAX, MP_MIN = 0, 1, 2, 3
 MP_ADD, MP_SUB, MP_MUL = 0, 1, 2
 MP_PAINN_FILTER_IMAGE_BYTES = 73728   # include/mpengine.h
 MP_CENT_MAX_ATOMS = 128               # include/mpengine.h: atoms per molecule of the charge solve
+MP_SBF_MAX_SPHERICAL, MP_SBF_MAX_RADIAL = 16, 64   # include/mpengine.h: spherical basis limits
 MP_FLAG_OOB, MP_FLAG_UNSORTED_COL0, MP_FLAG_UNSORTED_COL1 = 1, 2, 4
 
 ACTIVATION_CODES = {
     None: 0, "linear": 0, "relu": 1, "kgcnn>shifted_softplus": 2, "shifted_softplus": 2, "softplus": 3,
     "swish": 4, "sigmoid": 5, "tanh": 6, "kgcnn>leaky_relu": 7, "leaky_relu": 7, "kgcnn>softplus2": 8, "softplus2": 8,
-    "selu": 9,
+    "selu": 9, "kgcnn>swish": 4,
 }
 
 P = c_void_p
@@ -165,6 +166,15 @@ _SIGNATURES = {
     "mp_cent_charge_grad_f32": [P, P, P, c_int64, c_int64, P, P, P, P, c_int, P, P, P],
     "mp_gauss_energy_f32": [P, P, P, P, c_int64, c_int64, P, c_int64, P, P, c_int, c_float, P, P],
     "mp_gauss_energy_grad_f32": [P, P, P, P, c_int64, c_int64, P, c_int64, P, P, P, P, P, c_int, c_float, P, P, P, P],
+    "mp_vector_angle_f32": [P, P, c_int64, P, P],
+    "mp_vector_angle_grad_f32": [P, P, c_int64, P, P, P, P],
+    "mp_edge_angle_f32": [P, c_int64, P, c_int64, P, P, P],
+    "mp_edge_angle_grad_ws_bytes": [c_int64, P],
+    "mp_edge_angle_grad_f32": [P, c_int64, P, c_int64, P, P, P, P, P, P, P, c_size_t, P, P],
+    "mp_spherical_basis_f32": [P, c_int64, P, P, c_int64, P, c_int, c_int, c_float, c_int, P, P, P],
+    "mp_spherical_basis_grad_f32": [P, c_int64, P, P, c_int64, P, P, P, c_int, c_int, c_float, c_int, P, P, P, P, P],
+    "mp_dimenet_triplet_f32": [P, c_int64, P, c_int, P, c_int64, P, P, P, c_int, P, c_int, P, P],
+    "mp_dimenet_triplet_grad_f32": [P, c_int64, P, c_int, P, c_int64, P, P, P, c_int, P, c_int, P, P, P, P],
 }
 _RESTYPES = {"mp_last_error": c_char_p}
 

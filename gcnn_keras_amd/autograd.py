@@ -969,3 +969,84 @@ class GaussElectrostatics(torch.autograd.Function):
                                       "(ElectrostaticEnergyGaussCharge) is not implemented")
         q_bar, x_bar = ctx.spec.grad(ctx.q, ctx.xyz, g, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
         return q_bar, x_bar, None
+
+
+# ---------------------------------------------------------------------------------------------------------- DimeNet++
+# First-order rules of csrc/mp_dimenet.hip (layers/geom.py EdgeAngle / VectorAngle, layers/conv/dimenet_conv.py).
+# The weights of the DimeNet++ layers stay frozen, so no weight gradients; a backward in grad mode (a create_graph
+# pass, i.e. a force loss) raises NotImplementedError, as the CENT rules do.
+
+def _first_order_only(what):
+    if torch.is_grad_enabled():
+        raise NotImplementedError("second derivative of %s (a force loss or a create_graph backward through DimeNet++) "
+                                  "is not implemented" % what)
+
+
+class VectorAngle(torch.autograd.Function):
+    """theta (T, 1) of two vector rows (``mp_vector_angle_f32``); backward ``mp_vector_angle_grad_f32``."""
+
+    @staticmethod
+    def forward(ctx, v1, v2):
+        from .layers.geom import vector_angle_raw
+        ctx.v1, ctx.v2 = v1.detach().contiguous(), v2.detach().contiguous()
+        return vector_angle_raw(ctx.v1, ctx.v2)
+
+    @staticmethod
+    def backward(ctx, g):
+        _first_order_only("VectorAngle")
+        t = int(ctx.v1.shape[0])
+        g1 = torch.empty_like(ctx.v1) if ctx.needs_input_grad[0] else None
+        g2 = torch.empty_like(ctx.v2) if ctx.needs_input_grad[1] else None
+        if t and (g1 is not None or g2 is not None):
+            _ffi.call("mp_vector_angle_grad_f32", _ffi.ptr(ctx.v1), _ffi.ptr(ctx.v2), t, _ffi.ptr(g.contiguous()),
+                      _ffi.ptr(g1), _ffi.ptr(g2), _ffi.stream())
+        return g1, g2
+
+
+class EdgeAngle(torch.autograd.Function):
+    """theta (T, 1) between the edge vectors of every angle pair (``spec``: layers/geom.py ``EdgeAngleSpec``); backward
+    v_bar (E, 3) added per edge over both angle columns' CSR (``mp_edge_angle_grad_f32``)."""
+
+    @staticmethod
+    def forward(ctx, v, spec):
+        ctx.v, ctx.spec = v.detach().contiguous(), spec
+        return spec.forward(ctx.v)
+
+    @staticmethod
+    def backward(ctx, g):
+        _first_order_only("EdgeAngle")
+        return ctx.spec.grad(ctx.v, g), None
+
+
+class SphericalBasis(torch.autograd.Function):
+    """sbf (T, L*R) of distances d (E, 1) and angles theta (T, 1) (``spec``: layers/conv/dimenet_conv.py
+    ``SphericalBasisSpec``); backward d_bar (E, 1) and theta_bar (T, 1), each only when asked."""
+
+    @staticmethod
+    def forward(ctx, d, theta, spec):
+        sbf, rbf_env = spec.forward(d, theta)
+        ctx.d, ctx.theta, ctx.spec, ctx.rbf_env = d.detach().contiguous(), theta.detach().contiguous(), spec, rbf_env
+        return sbf
+
+    @staticmethod
+    def backward(ctx, g):
+        _first_order_only("SphericalBasisLayer")
+        d_bar, theta_bar = ctx.spec.grad(ctx.d, ctx.theta, ctx.rbf_env, g, ctx.needs_input_grad[0],
+                                         ctx.needs_input_grad[1])
+        return d_bar, theta_bar, None
+
+
+class DimeTriplet(torch.autograd.Function):
+    """Fused triplet step of DimNetInteractionPPBlock, out (E, 64) of xdown (E, 64) and sbf (T, L*R) (``spec``:
+    layers/conv/dimenet_conv.py ``TripletSpec``, frozen W_sbf1 / W_sbf2); backward xdown_bar and sbf_bar."""
+
+    @staticmethod
+    def forward(ctx, xdown, sbf, spec):
+        ctx.xdown, ctx.sbf, ctx.spec = xdown.detach().contiguous(), sbf.detach().contiguous(), spec
+        return spec.forward(ctx.xdown, ctx.sbf)
+
+    @staticmethod
+    def backward(ctx, g):
+        _first_order_only("the DimNetInteractionPPBlock triplet step")
+        x_bar, s_bar = ctx.spec.grad(ctx.xdown, ctx.sbf, g, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        return x_bar, s_bar, None

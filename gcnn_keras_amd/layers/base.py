@@ -46,6 +46,14 @@ def weight_epoch():
     return _weight_epoch[0]
 
 
+def _orthogonal(rng, shape):
+    """Keras Orthogonal: QR of a normal matrix (sign-fixed), rows >= cols handled by transposition."""
+    rows, cols = int(np.prod(shape[:-1])), shape[-1]
+    q, r = np.linalg.qr(rng.normal(size=(max(rows, cols), min(rows, cols))))
+    q = q * np.sign(np.diag(r))
+    return (q if rows >= cols else q.T).reshape(shape).astype(np.float32)
+
+
 class Layer:
     """Just enough of ``ks.layers.Layer``: naming, lazy build, weights, ``get_config``.
 
@@ -98,12 +106,21 @@ class Layer:
             fan_in, fan_out = fan if fan is not None else (shape[0], shape[-1])
             limit = np.sqrt(6.0 / (fan_in + fan_out))
             arr = rng.uniform(-limit, limit, size=shape).astype(np.float32)
+        elif isinstance(initializer, dict):
+            # Keras' serialised form; only RandomUniform {"minval", "maxval"} (DimeNetPP's embedding) is built
+            cls_name, cfg = initializer.get("class_name"), initializer.get("config") or {}
+            if cls_name not in ("RandomUniform", "random_uniform"):
+                raise ValueError("Unsupported initializer %r" % (initializer,))
+            arr = rng.uniform(float(cfg.get("minval", -0.05)), float(cfg.get("maxval", 0.05)),
+                              size=shape).astype(np.float32)
         elif initializer in ("orthogonal", "Orthogonal"):
-            # Keras Orthogonal: QR of a normal matrix (sign-fixed), rows >= cols handled by transposition
-            rows, cols = int(np.prod(shape[:-1])), shape[-1]
-            q, r = np.linalg.qr(rng.normal(size=(max(rows, cols), min(rows, cols))))
-            q = q * np.sign(np.diag(r))
-            arr = (q if rows >= cols else q.T).reshape(shape).astype(np.float32)
+            arr = _orthogonal(rng, shape)
+        elif initializer in ("kgcnn>glorot_orthogonal", "glorot_orthogonal", "GlorotOrthogonal"):
+            # kgcnn/ops/initializer.py GlorotOrthogonal: Orthogonal rescaled to variance 1 / max(1, mean fan)
+            w = _orthogonal(rng, shape).astype(np.float64)
+            fan_in, fan_out = (shape[0], shape[1]) if len(shape) == 2 else (shape[0], shape[0])
+            scale = 1.0 / max(1.0, (fan_in + fan_out) / 2.0)
+            arr = (w * np.sqrt(scale / np.var(w))).astype(np.float32)
         elif initializer in ("uniform", "RandomUniform", "random_uniform"):
             arr = rng.uniform(-0.05, 0.05, size=shape).astype(np.float32)
         else:

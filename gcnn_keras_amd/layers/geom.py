@@ -277,3 +277,115 @@ class CosCutOffEnvelope(GraphBaseLayer):
         config = super().get_config()
         config.update({"cutoff": self.cutoff})
         return config
+
+
+def vector_angle_raw(v1, v2):
+    """theta (T, 1) = atan2(|v1 x v2|, v1 . v2) of two contiguous (T, 3) tensors (``mp_vector_angle_f32``)."""
+    t = int(v1.shape[0])
+    out = torch.empty((t, 1), dtype=torch.float32, device=v1.device)
+    if t:
+        _ffi.call("mp_vector_angle_f32", _ffi.ptr(v1), _ffi.ptr(v2), t, _ffi.ptr(out), _ffi.stream())
+    return out
+
+
+class VectorAngle(GraphBaseLayer):
+    r"""Angle between two vectors, :math:`\theta = \tan^{-1}(|\vec{v}_1 \times \vec{v}_2| / \vec{v}_1 \cdot \vec{v}_2)`
+    (kgcnn/layers/geom.py:382-446) on ``mp_vector_angle_f32``; output ``(batch, [M], 1)``.  At collinear vectors the
+    reverse gives a zero gradient where the reference's ``tf.norm`` gradient is NaN."""
+
+    weight_gradients = True   # layers/base.py: the layer has no weights
+
+    @staticmethod
+    def _compute_vector_angle(inputs: list):
+        v1, v2 = inputs[0], inputs[1]
+        _ffi.require_device(v1, v2)
+        if tuple(v1.shape) != tuple(v2.shape) or v1.dim() != 2 or int(v1.shape[-1]) != 3:
+            raise ValueError("VectorAngle expects two (batch, [M], 3) tensors, got %s and %s"
+                             % (tuple(v1.shape), tuple(v2.shape)))
+        from ..autograd import VectorAngle as AngleFn, needs_grad
+        if needs_grad(v1, v2):
+            return AngleFn.apply(v1, v2)
+        return vector_angle_raw(v1.contiguous(), v2.contiguous())
+
+    def call(self, inputs, **kwargs):
+        return self.map_values(self._compute_vector_angle, list(inputs))
+
+
+class EdgeAngleSpec:
+    """One EdgeAngle call bound to an angle index plan against the edges: ``forward`` (E, 3) -> (T, 1) and ``grad``."""
+
+    def __init__(self, plan, scale):
+        self.plan, self.scale = plan, scale
+
+    def forward(self, v):
+        out = torch.empty((self.plan.M, 1), dtype=torch.float32, device=v.device)
+        _ffi.call("mp_edge_angle_f32", _ffi.ptr(v), self.plan.N, _ffi.ptr(self.plan.cols), self.plan.M,
+                  _ffi.ptr(self.scale), _ffi.ptr(out), _ffi.stream())
+        return out
+
+    def grad(self, v, g):
+        import ctypes
+        nbytes = ctypes.c_size_t(0)
+        _ffi.call("mp_edge_angle_grad_ws_bytes", self.plan.M, ctypes.byref(nbytes))
+        ws = torch.empty((max(nbytes.value, 4) // 4,), dtype=torch.float32, device=v.device)
+        v_bar = torch.empty_like(v)
+        ptr0, perm0, _ = self.plan.csr(0)
+        ptr1, perm1, _ = self.plan.csr(1)
+        _ffi.call("mp_edge_angle_grad_f32", _ffi.ptr(v), self.plan.N, _ffi.ptr(self.plan.cols), self.plan.M,
+                  _ffi.ptr(ptr0), _ffi.ptr(perm0), _ffi.ptr(ptr1), _ffi.ptr(perm1), _ffi.ptr(self.scale),
+                  _ffi.ptr(g.contiguous()), _ffi.ptr(ws), nbytes.value, _ffi.ptr(v_bar), _ffi.stream())
+        return v_bar
+
+
+def angle_plan(idx, edges, layer):
+    """Index plan of an angle list ``(batch, [T], 2)`` against the edge partition of ``edges``; out-of-range pairs raise
+    ``IndexError`` (the DimeNet++ kernels read both edges of every pair)."""
+    _ffi.require_device(edges.values, idx.values)
+    if idx.values.dim() != 2 or int(idx.values.shape[-1]) != 2:
+        raise ValueError("%s expects angle indices of shape (batch, [T], 2)" % layer.name)
+    plan = idx.index_plan(edges)
+    plan.validate()
+    return plan
+
+
+class EdgeAngle(GraphBaseLayer):
+    r"""Angle between the vectors of the two edges of every angle pair ``(n, m)`` (kgcnn/layers/geom.py:450-510): the
+    reference's ``GatherNodesSelection([0, 1])`` + ``VectorAngle`` as one kernel, ``mp_edge_angle_f32``.
+    ``vector_scale``: two scales (scalars or 3-vectors) for the vectors of ``n`` and ``m``.  Output
+    ``(batch, [T], 1)``."""
+
+    weight_gradients = True   # layers/base.py: the layer has no weights
+
+    def __init__(self, vector_scale: list = None, **kwargs):
+        super().__init__(**kwargs)
+        self.vector_scale = vector_scale
+        if vector_scale:
+            assert len(vector_scale) == 2, "Need scale for both vectors to compute angle."
+        self._scale_host = None
+        if vector_scale:
+            self._scale_host = np.concatenate([np.broadcast_to(np.asarray(s, dtype=np.float32), (3,))
+                                               for s in vector_scale]).astype(np.float32)
+        self._scale_dev = None
+
+    def _scale(self, device):
+        if self._scale_host is None:
+            return None
+        if self._scale_dev is None or self._scale_dev.device != device:
+            self._scale_dev = torch.from_numpy(self._scale_host.copy()).to(device)
+        return self._scale_dev
+
+    def call(self, inputs, **kwargs):
+        vec, idx = self.assert_ragged_input_rank(list(inputs))
+        v = vec.values
+        if v.dtype != torch.float32 or v.dim() != 2 or int(v.shape[-1]) != 3:
+            raise ValueError("EdgeAngle expects float32 edge vectors of shape (batch, [M], 3)")
+        spec = EdgeAngleSpec(angle_plan(idx, vec, self), self._scale(v.device))
+        from ..autograd import EdgeAngle as AngleFn, needs_grad
+        if needs_grad(v):
+            return idx.with_values(AngleFn.apply(v, spec))
+        return idx.with_values(spec.forward(v.contiguous()))
+
+    def get_config(self):
+        config = super().get_config()
+        config.update({"vector_scale": self.vector_scale})
+        return config

@@ -447,3 +447,84 @@ def hdnnp4th_batch(num_graphs=128, seed=4567, sigma=1.5, min_distance=0.9, mixed
         "esp": np.concatenate(esp), "esp_grad": np.concatenate(esp_grad, axis=0),
         "mm_positions": np.stack(mm_x), "mm_charges": np.stack(mm_q),
     }
+
+
+# ---------------------------------------------------------------------------------------------------------- DimeNet++
+# The model section of the reference's MD17 DimeNet++ force-field runs (training/results/MD17Dataset/
+# DimeNetPP_EnergyForceModel/DimeNetPP_hyper_*.json): the energy model inside EnergyForceModel.
+DIMENET_MD17 = {
+    "name": "DimeNetPPEnergy",
+    "inputs": [{"shape": [None], "name": "z", "dtype": "float32", "ragged": True},
+               {"shape": [None, 3], "name": "R", "dtype": "float32", "ragged": True},
+               {"shape": [None, 2], "name": "range_indices", "dtype": "int64", "ragged": True},
+               {"shape": [None, 2], "name": "angle_indices", "dtype": "int64", "ragged": True}],
+    "input_embedding": {"node": {"input_dim": 95, "output_dim": 128,
+                                 "embeddings_initializer": {"class_name": "RandomUniform",
+                                                            "config": {"minval": -1.7320508075688772,
+                                                                       "maxval": 1.7320508075688772}}}},
+    "emb_size": 128, "out_emb_size": 256, "int_emb_size": 64, "basis_emb_size": 8, "num_blocks": 4,
+    "num_spherical": 7, "num_radial": 6, "cutoff": 5.0, "envelope_exponent": 5, "num_before_skip": 1,
+    "num_after_skip": 2, "num_dense_output": 3, "num_targets": 1, "extensive": False, "output_init": "zeros",
+    "activation": "swish", "verbose": 10, "output_embedding": "graph", "use_output_mlp": False, "output_mlp": {},
+}
+
+
+def angle_pairs(idx, edge_pairing="jk"):
+    """Edge pairs ``(n, m)`` forming an angle in one molecule's edge list: the third output of kgcnn/graph/adj.py::
+    get_angle_indices with its defaults (no multi, self or reverse edges, sorted).  With "jk", edge ``n = (i, j)`` pairs
+    with every ``m = (j, k)``; the pairs are ordered by n, then m."""
+    idx = np.asarray(idx, dtype=np.int64).reshape(-1, 2)
+    if len(idx) == 0:
+        return np.zeros((0, 2), np.int64)
+    pos_fix = 1 if edge_pairing[0] == "k" else 0
+    pos_ij = 0 if "i" in edge_pairing else 1
+    a, b = idx[:, None, :], idx[None, :, :]
+    mask = b[..., pos_fix] == a[..., pos_ij]
+    mask &= (b[..., 0] != a[..., 0]) | (b[..., 1] != a[..., 1])      # multi edges
+    mask &= (b[..., 0] != a[..., 1]) | (b[..., 1] != a[..., 0])      # reverse edges
+    np.fill_diagonal(mask, False)                                    # self
+    n, m = np.nonzero(mask)
+    return np.stack([n, m], axis=-1).astype(np.int64)
+
+
+def dimenet_batch(num_graphs=64, seed=2345, min_distance=None, sizes=None, max_distance=5.0, **kwargs):
+    """``md17_like_batch`` plus the DimeNet++ angle input: ``angle_indices`` (edge pairs of ``angle_pairs``, local to
+    each molecule's edge list) and ``angle_splits``.  With ``min_distance`` (or ``sizes``, atoms per molecule) the
+    molecules are drawn with no atom pair closer than ``min_distance`` instead (aspirin's elements, cycled)."""
+    if min_distance is None and sizes is None:
+        b = md17_like_batch(num_graphs=num_graphs, seed=seed, max_distance=max_distance, **kwargs)
+    else:
+        rng = np.random.default_rng(seed)
+        sizes = [21] * num_graphs if sizes is None else list(sizes)
+        xs = [_molecule(rng, n, kwargs.get("sigma", 1.7), min_distance or 0.0) for n in sizes]
+        es = [radius_graph(x, max_distance=max_distance, max_neighbours=10000).reshape(-1, 2) for x in xs]
+        b = {"node_number": np.concatenate([np.resize(ASPIRIN_Z, n) for n in sizes]).astype(np.float32),
+             "node_coordinates": np.concatenate(xs, axis=0).astype(np.float32),
+             "edge_indices": np.concatenate(es, axis=0).reshape(-1, 2).astype(np.int64),
+             "node_splits": _splits(sizes), "edge_splits": _splits([len(e) for e in es])}
+    es = b["edge_splits"]
+    pairs = [angle_pairs(b["edge_indices"][es[g]:es[g + 1]]) for g in range(len(es) - 1)]
+    b["angle_indices"] = np.concatenate(pairs, axis=0).reshape(-1, 2).astype(np.int64)
+    b["angle_splits"] = _splits([len(p) for p in pairs])
+    return b
+
+
+def dimenet_params(model, seed=13):
+    """Random weights for a built DimeNet++ ``model`` in ``model.weights`` order: Glorot-uniform kernels (the output
+    kernels too, which ``output_init="zeros"`` would leave at 0 and the energy identically 0), biases in +-0.1, the
+    embedding in +-sqrt(3), Bessel frequencies ``pi * (1..R)``."""
+    rng = np.random.default_rng(seed)
+    p = {}
+    for i, (name, t) in enumerate(model.weights):
+        shape = tuple(int(s) for s in t.shape)
+        leaf = name.rsplit("/", 1)[-1]
+        if leaf == "embeddings":
+            v = rng.uniform(-np.sqrt(3.0), np.sqrt(3.0), size=shape)
+        elif leaf == "frequencies":
+            v = np.pi * np.arange(1, shape[0] + 1)
+        elif leaf == "bias":
+            v = rng.uniform(-0.1, 0.1, size=shape)
+        else:
+            v = glorot_uniform(rng, shape[0], shape[-1], shape=shape)
+        p["%03d/%s" % (i, name)] = np.asarray(v, dtype=np.float32)
+    return p
