@@ -175,6 +175,13 @@ _SIGNATURES = {
     "mp_spherical_basis_grad_f32": [P, c_int64, P, P, c_int64, P, P, P, c_int, c_int, c_float, c_int, P, P, P, P, P],
     "mp_dimenet_triplet_f32": [P, c_int64, P, c_int, P, c_int64, P, P, P, c_int, P, c_int, P, P],
     "mp_dimenet_triplet_grad_f32": [P, c_int64, P, c_int, P, c_int64, P, P, P, c_int, P, c_int, P, P, P, P],
+    "mp_position_encoding_f32": [P, c_int64, P, c_int, c_int, P, P],
+    "mp_position_encoding_grad_f32": [P, c_int64, P, c_int, c_int, P, P, P],
+    "mp_egnn_edge_ws_bytes": [c_int64, P],
+    "mp_egnn_edge_f32": [P, P, c_int64, P, P, c_int64, P, P, P, c_int, c_int, P, P, c_int, P, P, c_int, P, P, c_int,
+                         c_float, P, c_size_t, P, P, P, P],
+    "mp_egnn_edge_grad_f32": [P, c_int64, P, P, c_int64, P, P, P, c_int, c_int, P, c_int, P, c_int, P, P, c_int,
+                              c_float, P, P, P],
 }
 _RESTYPES = {"mp_last_error": c_char_p}
 

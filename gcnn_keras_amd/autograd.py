@@ -976,10 +976,10 @@ class GaussElectrostatics(torch.autograd.Function):
 # The weights of the DimeNet++ layers stay frozen, so no weight gradients; a backward in grad mode (a create_graph
 # pass, i.e. a force loss) raises NotImplementedError, as the CENT rules do.
 
-def _first_order_only(what):
+def _first_order_only(what, model="DimeNet++"):
     if torch.is_grad_enabled():
-        raise NotImplementedError("second derivative of %s (a force loss or a create_graph backward through DimeNet++) "
-                                  "is not implemented" % what)
+        raise NotImplementedError("second derivative of %s (a force loss or a create_graph backward through %s) "
+                                  "is not implemented" % (what, model))
 
 
 class VectorAngle(torch.autograd.Function):
@@ -1050,3 +1050,45 @@ class DimeTriplet(torch.autograd.Function):
         _first_order_only("the DimNetInteractionPPBlock triplet step")
         x_bar, s_bar = ctx.spec.grad(ctx.xdown, ctx.sbf, g, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
         return x_bar, s_bar, None
+
+
+# --------------------------------------------------------------------------------------------------------------- EGNN
+# First-order rules of csrc/mp_egnn.hip (layers/geom.py PositionEncodingBasisLayer, layers/conv/egnn_conv.py).  The fused
+# edge step reads its weights in place and has no rule for them: the layer takes the layer sequence when one of them
+# requires grad.  A backward in grad mode (a create_graph pass, i.e. a force loss) raises NotImplementedError.
+
+class PositionEncoding(torch.autograd.Function):
+    """[sin(x s) | cos(x s)] (M, 2K) of x (M, 1); backward x_bar = sum_k s_k (g_sin cos - g_cos sin)."""
+
+    @staticmethod
+    def forward(ctx, x, scales, interleave):
+        from .layers.geom import position_encoding_raw
+        ctx.x, ctx.scales, ctx.interleave = x.detach().contiguous(), scales, interleave
+        return position_encoding_raw(ctx.x, scales, interleave)
+
+    @staticmethod
+    def backward(ctx, g):
+        _first_order_only("PositionEncodingBasisLayer", "EGNN")
+        m, k = int(ctx.x.shape[0]), int(ctx.scales.shape[0])
+        x_bar = torch.empty_like(ctx.x)
+        _ffi.call("mp_position_encoding_grad_f32", _ffi.ptr(ctx.x), m, _ffi.ptr(ctx.scales), k,
+                  1 if ctx.interleave else 0, _ffi.ptr(g.contiguous()), _ffi.ptr(x_bar), _ffi.stream())
+        return x_bar, None, None
+
+
+class EgnnEdge(torch.autograd.Function):
+    """Fused EGNN edge step, m_i (N, 128) of the node projections Pa, Pb (N, 128) and the norm output x (E, 1) (``spec``:
+    layers/conv/egnn_conv.py ``EdgeStepSpec``, frozen weights); backward Pa_bar, Pb_bar and x_bar from the saved
+    pre-activations."""
+
+    @staticmethod
+    def forward(ctx, pa, pb, x, spec):
+        ctx.x, ctx.spec = x.detach().contiguous(), spec
+        out, ctx.z1, ctx.z2 = spec.forward(pa.detach().contiguous(), pb.detach().contiguous(), ctx.x, save=True)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        _first_order_only("the fused EGNN edge step", "EGNN")
+        a_bar, b_bar, x_bar = ctx.spec.grad(ctx.x, ctx.z1, ctx.z2, g, *ctx.needs_input_grad[:3])
+        return a_bar, b_bar, x_bar, None

@@ -389,3 +389,73 @@ class EdgeAngle(GraphBaseLayer):
         config = super().get_config()
         config.update({"vector_scale": self.vector_scale})
         return config
+
+
+def position_encoding_scales(dim_half, wave_length_min, num_mult):
+    """``2 pi exp(-log(num_mult) i / (dim_half - 1) - log(wave_length_min))`` (dim_half,), every step rounded to float32
+    as the reference's float32 graph builds it (kgcnn/layers/geom.py:677-681)."""
+    steps = np.arange(dim_half, dtype=np.float32) / np.float32(dim_half - 1)
+    log_num, log_wave = np.float32(-np.log(num_mult)), np.float32(-np.log(wave_length_min))
+    freq = np.exp((log_num * steps + log_wave).astype(np.float32)).astype(np.float32)
+    return (freq * np.float32(np.pi * 2.0)).astype(np.float32)
+
+
+def position_encoding_raw(x, scales, interleave):
+    """(M, 2K) encoding of contiguous x (M, 1) on ``mp_position_encoding_f32``."""
+    m, k = int(x.shape[0]), int(scales.shape[0])
+    out = torch.empty((m, 2 * k), dtype=torch.float32, device=x.device)
+    _ffi.call("mp_position_encoding_f32", _ffi.ptr(x), m, _ffi.ptr(scales), k, 1 if interleave else 0, _ffi.ptr(out),
+              _ffi.stream())
+    return out
+
+
+class PositionEncodingBasisLayer(GraphBaseLayer):
+    r"""Positional (Fourier) encoding of a distance (kgcnn/layers/geom.py:596-713): ``[sin(x s_k) | cos(x s_k)]`` with
+    ``s_k = 2 pi / (wave_length_min num_mult^(k / (dim_half - 1)))``, or sin and cos interleaved per ``k``
+    (``interleave_sin_cos``), on ``mp_position_encoding_f32``; input ``(batch, [K], 1)``, output ``(batch, [K], 2
+    dim_half)``.  ``include_frequencies=True`` is a ``TypeError`` inside the reference (``tf.concat(..., dim=-1)``) and
+    raises ``NotImplementedError`` here."""
+
+    weight_gradients = True   # layers/base.py: the layer has no weights
+
+    def __init__(self, dim_half: int = 10, wave_length_min: float = 1, num_mult=100, include_frequencies: bool = False,
+                 interleave_sin_cos: bool = False, **kwargs):
+        super().__init__(**kwargs)
+        self.dim_half = dim_half
+        self.num_mult = num_mult
+        self.wave_length_min = wave_length_min
+        self.include_frequencies = include_frequencies
+        self.interleave_sin_cos = interleave_sin_cos
+        if self.num_mult <= 1:
+            raise ValueError("`num_mult` must be >1. Reduce `wave_length_min` if necessary.")
+        if self.dim_half <= 1:
+            raise ValueError("`dim_half` must be > 1.")
+        if self.include_frequencies:
+            raise NotImplementedError("PositionEncodingBasisLayer(include_frequencies=True) fails in the reference "
+                                      "(tf.concat(..., dim=-1)) and is not implemented")
+        self.scales_host = position_encoding_scales(int(dim_half), wave_length_min, num_mult)
+        self._scales = None
+
+    def scales(self, device):
+        if self._scales is None or self._scales.device != device:
+            self.__dict__["_scales"] = torch.from_numpy(self.scales_host.copy()).to(device)
+        return self._scales
+
+    def _compute_fourier_encoding(self, inputs):
+        _ffi.require_device(inputs)
+        if inputs.dtype != torch.float32 or inputs.dim() != 2 or int(inputs.shape[-1]) != 1:
+            raise ValueError("PositionEncodingBasisLayer expects float32 distances of shape (batch, [K], 1)")
+        scales = self.scales(inputs.device)
+        from ..autograd import PositionEncoding, needs_grad
+        if needs_grad(inputs):
+            return PositionEncoding.apply(inputs, scales, bool(self.interleave_sin_cos))
+        return position_encoding_raw(inputs.contiguous(), scales, self.interleave_sin_cos)
+
+    def call(self, inputs, **kwargs):
+        return self.map_values(self._compute_fourier_encoding, inputs)
+
+    def get_config(self):
+        config = super().get_config()
+        config.update({"dim_half": self.dim_half, "wave_length_min": self.wave_length_min, "num_mult": self.num_mult,
+                       "include_frequencies": self.include_frequencies, "interleave_sin_cos": self.interleave_sin_cos})
+        return config

@@ -528,3 +528,86 @@ def dimenet_params(model, seed=13):
             v = glorot_uniform(rng, shape[0], shape[-1], shape=shape)
         p["%03d/%s" % (i, name)] = np.asarray(v, dtype=np.float32)
     return p
+
+
+# --------------------------------------------------------------------------------------------------------------- EGNN
+# The model sections of the reference's EGNN runs: training/results/MD17Dataset/EGNN_EnergyForceModel/
+# EGNN_hyper_aspirin_ccsd.json (the energy model inside EnergyForceModel) and training/results/QM9Dataset/EGNN/
+# EGNN_hyper_U0.json (the same without the position encoding).
+EGNN_MD17 = {
+    "name": "EGNNEnergy",
+    "inputs": [{"shape": [None, 15], "name": "node_attributes", "dtype": "float32", "ragged": True},
+               {"shape": [None, 3], "name": "R", "dtype": "float32", "ragged": True},
+               {"shape": [None, 2], "name": "range_indices", "dtype": "int64", "ragged": True},
+               {"shape": [None, 1], "name": "range_attributes", "dtype": "int64", "ragged": True}],
+    "input_embedding": {"node": {"input_dim": 95, "output_dim": 128}, "edge": {"input_dim": 95, "output_dim": 128}},
+    "depth": 7,
+    "node_mlp_initialize": {"units": 128, "activation": "linear"},
+    "euclidean_norm_kwargs": {"keepdims": True, "axis": 2, "square_norm": True},
+    "use_edge_attributes": False,
+    "edge_mlp_kwargs": {"units": [128, 128], "activation": ["swish", "swish"]},
+    "edge_attention_kwargs": {"units": 1, "activation": "sigmoid"},
+    "use_normalized_difference": False,
+    "expand_distance_kwargs": {"dim_half": 64},
+    "coord_mlp_kwargs": None, "pooling_coord_kwargs": None,
+    "pooling_edge_kwargs": {"pooling_method": "sum"},
+    "node_normalize_kwargs": None, "use_node_attributes": False,
+    "node_mlp_kwargs": {"units": [128, 128], "activation": ["swish", "linear"]},
+    "use_skip": True, "verbose": 10,
+    "node_decoder_kwargs": {"units": [128, 128], "activation": ["swish", "linear"]},
+    "node_pooling_kwargs": {"pooling_method": "sum"},
+    "output_embedding": "graph", "output_to_tensor": True,
+    "output_mlp": {"use_bias": [True, True], "units": [128, 1], "activation": ["swish", "linear"]},
+}
+
+EGNN_QM9 = dict(EGNN_MD17, name="EGNN", expand_distance_kwargs=None,
+                inputs=[dict(EGNN_MD17["inputs"][0]), dict(EGNN_MD17["inputs"][1], name="node_coordinates"),
+                        dict(EGNN_MD17["inputs"][2]), dict(EGNN_MD17["inputs"][3])])
+
+
+def atomic_charge_representation(numbers, one_hot=(1, 6, 7, 8, 9), charge_scale=9.0, charge_power=2):
+    """EGNN's node attributes (the reference's ``atomic_charge_representation`` preprocessor with its defaults): for
+    every listed element a block ``[1, z / scale, (z / scale)^2]`` that is zero unless the atom is that element; shape
+    ``(N, len(one_hot) * (charge_power + 1))`` float32."""
+    z = np.asarray(numbers, dtype=np.float64).reshape(-1)
+    out = np.zeros((len(z), len(one_hot), charge_power + 1))
+    for j, element in enumerate(one_hot):
+        rows = z == element
+        for p in range(charge_power + 1):
+            out[rows, j, p] = (z[rows] / charge_scale) ** p
+    return out.reshape(len(z), -1).astype(np.float32)
+
+
+def egnn_batch(num_graphs=64, seed=2345, min_distance=0.9, sizes=None, max_distance=10.0, sigma=1.7):
+    """MD17-shaped EGNN inputs: aspirin-composition molecules (21 atoms, or ``sizes`` atoms each with aspirin's elements
+    cycled) with no atom pair closer than ``min_distance``, ``node_attributes`` (N, 15) of
+    :func:`atomic_charge_representation`, and every pair within ``max_distance`` as a directed edge (10 A in the
+    reference's runs: the graphs are fully connected)."""
+    rng = np.random.default_rng(seed)
+    sizes = [21] * num_graphs if sizes is None else list(sizes)
+    xs = [_molecule(rng, n, sigma, min_distance or 0.0) for n in sizes]
+    es = [radius_graph(x, max_distance=max_distance, max_neighbours=10000).reshape(-1, 2) for x in xs]
+    numbers = np.concatenate([np.resize(ASPIRIN_Z, n) for n in sizes]).astype(np.float32) if sizes else \
+        np.zeros(0, np.float32)
+    return {"node_number": numbers, "node_attributes": atomic_charge_representation(numbers),
+            "node_coordinates": np.concatenate(xs, axis=0).astype(np.float32).reshape(-1, 3),
+            "edge_indices": np.concatenate(es, axis=0).reshape(-1, 2).astype(np.int64),
+            "node_splits": _splits(sizes), "edge_splits": _splits([len(e) for e in es])}
+
+
+def egnn_params(model, seed=14):
+    """Random weights for a built EGNN ``model`` in ``model.weights`` order: Glorot-uniform kernels, biases in +-0.1,
+    embeddings in +-0.05."""
+    rng = np.random.default_rng(seed)
+    p = {}
+    for i, (name, t) in enumerate(model.weights):
+        shape = tuple(int(s) for s in t.shape)
+        leaf = name.rsplit("/", 1)[-1]
+        if leaf == "embeddings":
+            v = rng.uniform(-0.05, 0.05, size=shape)
+        elif leaf == "bias":
+            v = rng.uniform(-0.1, 0.1, size=shape)
+        else:
+            v = glorot_uniform(rng, shape[0], shape[-1], shape=shape)
+        p["%03d/%s" % (i, name)] = np.asarray(v, dtype=np.float32)
+    return p

@@ -1,0 +1,149 @@
+"""Differentiable torch-CPU restatement of EGNN (kgcnn/literature/EGNN.py:130-201 and kgcnn/layers/geom.py:596-713), in
+float64 or float32: the budget and the float32 twin of the GPU tests.  No engine imports.  Forces come from autograd.
+Weights are consumed in ``model.weights`` order of ``gcnn_keras_amd.literature.EGNN.make_model`` (edge embedding, node
+embedding, start MLP, per block edge MLP / attention / coordinate MLP / node MLP, decoder, output MLP); ``cfg`` is the
+merged configuration (``model.config``).
+"""
+import numpy as np
+import torch
+
+ACTIVATIONS = {
+    None: lambda x: x, "linear": lambda x: x, "swish": lambda x: x * torch.sigmoid(x), "sigmoid": torch.sigmoid,
+    "tanh": torch.tanh, "relu": torch.relu, "softplus": torch.nn.functional.softplus,
+}
+
+
+def encoding_scales(dim_half=10, wave_length_min=1, num_mult=100):
+    """The reference's float32 frequency table (geom.py:677-681), every step rounded to float32."""
+    steps = np.arange(dim_half, dtype=np.float32) / np.float32(dim_half - 1)
+    freq = np.exp((np.float32(-np.log(num_mult)) * steps + np.float32(-np.log(wave_length_min))).astype(np.float32))
+    return (freq.astype(np.float32) * np.float32(np.pi * 2.0)).astype(np.float32)
+
+
+def position_encoding(x, dtype, dim_half=10, wave_length_min=1, num_mult=100, interleave=False):
+    """(M, 2 dim_half) of x (M, 1): the float32 scales are exact inputs to both precisions."""
+    arg = x * torch.tensor(encoding_scales(dim_half, wave_length_min, num_mult), dtype=dtype)[None, :]
+    if interleave:
+        return torch.stack([torch.sin(arg), torch.cos(arg)], dim=-1).reshape(arg.shape[0], -1)
+    return torch.cat([torch.sin(arg), torch.cos(arg)], dim=-1)
+
+
+def flat_edges(b):
+    """Flat (batch-shifted) edge indices (E, 2) of a synth.egnn_batch."""
+    ns, es = b["node_splits"], b["edge_splits"]
+    ei = b["edge_indices"].copy()
+    for g in range(len(ns) - 1):
+        ei[es[g]:es[g + 1]] += ns[g]
+    return ei
+
+
+def _listed(value, n):
+    return list(value) if isinstance(value, (list, tuple)) else [value] * n
+
+
+class _Weights:
+    def __init__(self, weights, dtype):
+        # tensors pass through (training: leaves of the caller's tape), arrays are converted
+        self.it = iter([w.to(dtype) if torch.is_tensor(w) else torch.tensor(np.asarray(w), dtype=dtype)
+                        for w in weights])
+
+    def mlp(self, kwargs):
+        """The (kernel, bias, activation) triples of one MLP, taken in order."""
+        units = _listed(kwargs["units"], 1)
+        acts = _listed(kwargs.get("activation"), len(units))
+        bias = _listed(kwargs.get("use_bias", True), len(units))
+        return [(next(self.it), next(self.it) if bias[i] else None, acts[i]) for i in range(len(units))]
+
+
+def run_mlp(layers, x):
+    for kernel, bias, act in layers:
+        x = x @ kernel
+        if bias is not None:
+            x = x + bias
+        x = ACTIVATIONS[act](x)
+    return x
+
+
+def seg_sum(x, idx, rows):
+    return torch.zeros((rows,) + tuple(x.shape[1:]), dtype=x.dtype).index_add(0, idx, x)
+
+
+def edge_norm(diff, kwargs):
+    s = (diff * diff).sum(-1, keepdim=True)
+    return s if kwargs.get("square_norm") else torch.sqrt(torch.relu(s))
+
+
+def edge_step(h, norm_x, ei, edge_mlp, att_mlp, dtype, expand=False, ed=None):
+    """(m_ij (E, F), m_i (N, F)) of one block's edge model with sum pooling (EGNN.py:151-174)."""
+    if expand:
+        norm_x = position_encoding(norm_x, dtype)
+    parts = [h[ei[:, 0]], h[ei[:, 1]], norm_x] + ([ed] if ed is not None else [])
+    m = run_mlp(edge_mlp, torch.cat(parts, dim=-1))
+    if att_mlp is not None:
+        m = run_mlp(att_mlp, m) * m
+    return m, seg_sum(m, ei[:, 0], int(h.shape[0]))
+
+
+def egnn_forward(weights, b, cfg, xyz=None, dtype=torch.float64, return_coordinates=False):
+    """Model output of EGNN on a synth.egnn_batch ``b`` (graph: (G, L); node: (N, L)); ``xyz``: coordinates tensor
+    (defaults to the batch's; a leaf when forces are wanted)."""
+    w = _Weights(weights, dtype)
+    ei = torch.from_numpy(flat_edges(b))
+    if xyz is None:
+        xyz = torch.tensor(b["node_coordinates"], dtype=dtype)
+    n_nodes = int(xyz.shape[0])
+    ed = None
+    if cfg["use_edge_attributes"]:
+        if len(cfg["inputs"][3]["shape"]) < 2:
+            ed = next(w.it)[torch.from_numpy(np.asarray(b["edge_attributes"])).long()]
+        else:
+            ed = torch.tensor(b["edge_attributes"], dtype=dtype)
+    elif len(cfg["inputs"][3]["shape"]) < 2:
+        next(w.it)    # the unused edge embedding still holds a table
+    if len(cfg["inputs"][0]["shape"]) < 2:
+        h0 = next(w.it)[torch.from_numpy(np.asarray(b["node_number"])).long()]
+    else:
+        h0 = torch.tensor(b["node_attributes"], dtype=dtype)
+    h = run_mlp(w.mlp(cfg["node_mlp_initialize"]), h0) if cfg["node_mlp_initialize"] else h0
+    x = xyz
+    degree = seg_sum(torch.ones(len(ei), dtype=dtype), ei[:, 0], n_nodes)
+    for _ in range(cfg["depth"]):
+        diff = x[ei[:, 0]] - x[ei[:, 1]]
+        norm_x = edge_norm(diff, cfg["euclidean_norm_kwargs"])
+        if cfg["use_normalized_difference"]:
+            d = torch.sqrt(torch.relu((diff * diff).sum(-1, keepdim=True)))
+            diff = torch.where(d > 0, diff / torch.where(d > 0, d, torch.ones_like(d)), torch.zeros_like(diff))
+        edge_mlp = w.mlp(cfg["edge_mlp_kwargs"]) if cfg["edge_mlp_kwargs"] else []
+        att_mlp = w.mlp(cfg["edge_attention_kwargs"]) if cfg["edge_attention_kwargs"] else None
+        m, m_i = edge_step(h, norm_x, ei, edge_mlp, att_mlp, dtype, expand=bool(cfg["expand_distance_kwargs"]), ed=ed)
+        if cfg["coord_mlp_kwargs"]:
+            trans = run_mlp(w.mlp(cfg["coord_mlp_kwargs"]), m) * diff
+            method = cfg["pooling_coord_kwargs"]["pooling_method"]
+            agg = seg_sum(trans, ei[:, 0], n_nodes)
+            if method in ("mean", "segment_mean"):
+                agg = agg / torch.clamp(degree, min=1.0)[:, None]
+            x = x + agg
+        assert cfg["pooling_edge_kwargs"]["pooling_method"] in ("sum", "segment_sum")
+        if cfg["node_mlp_kwargs"]:
+            m_i = torch.cat([h, m_i] + ([h0] if cfg["use_node_attributes"] else []), dim=-1)
+            m_i = run_mlp(w.mlp(cfg["node_mlp_kwargs"]), m_i)
+        h = h + m_i if cfg["use_skip"] else m_i
+    n = run_mlp(w.mlp(cfg["node_mlp_kwargs"]), h) if cfg["node_decoder_kwargs"] else h   # EGNN.py:188-189
+    if return_coordinates:
+        return x
+    if cfg["output_embedding"] == "graph":
+        ns = b["node_splits"]
+        graph = torch.from_numpy(np.repeat(np.arange(len(ns) - 1), np.diff(ns)))
+        assert cfg["node_pooling_kwargs"]["pooling_method"] in ("sum", "segment_sum")
+        n = seg_sum(n, graph, len(ns) - 1)
+    out = run_mlp(w.mlp(cfg["output_mlp"]), n)
+    assert next(w.it, None) is None, "weights left over"
+    return out
+
+
+def energy_forces(weights, b, cfg, dtype=torch.float64):
+    """(E (G, 1), F = -dE/dx (N, 3)) of the restatement."""
+    xyz = torch.tensor(b["node_coordinates"], dtype=dtype, requires_grad=True)
+    e = egnn_forward(weights, b, cfg, xyz=xyz, dtype=dtype)
+    (g,) = torch.autograd.grad(e.sum(), xyz)
+    return e.detach(), -g

@@ -1,0 +1,470 @@
+"""EGNN on the engine (csrc/mp_egnn.hip): the position encoding and its reverse, the fused edge step against the layer
+sequence and against the torch restatement (tests/egnn_reference.py, float32 with the float64 twin as budget), the whole
+model, forces through EnergyForceModel, energy training, determinism, replay and the guards."""
+import numpy as np
+import pytest
+import torch
+
+import egnn_reference as ref
+from gcnn_keras_amd import _ffi, synth
+from gcnn_keras_amd.layers.conv.egnn_conv import FusedEdgeStep
+from gcnn_keras_amd.layers.gather import GatherEmbeddingSelection
+from gcnn_keras_amd.layers.geom import EuclideanNorm, NodePosition, PositionEncodingBasisLayer
+from gcnn_keras_amd.layers.mlp import GraphMLP
+from gcnn_keras_amd.layers.modules import LazyConcatenate, LazyMultiply, LazySubtract
+from gcnn_keras_amd.layers.pooling import PoolingLocalEdges
+from gcnn_keras_amd.literature import EGNN
+from gcnn_keras_amd.model.force import EnergyForceModel
+from gcnn_keras_amd.ragged import RaggedTensor
+from parity import assert_forces_close, assert_rows_close, rowwise_rel
+
+pytestmark = pytest.mark.gpu
+
+# aspirin-sized molecules, a lone atom (a node without edges), an empty graph in the middle and at the end
+MIXED = [21, 1, 3, 0, 21, 12, 2, 0]
+
+# sin(x s) at x s ~ 600 moves by an ulp of the argument (6e-5) as soon as d^2 was summed in another order or the product
+# x s was rounded in float32: ANY float32 evaluation sits that far from float64, so these rows are held to the float64
+# twin as budget with caps above parity.py's 5e-5.  Measured distance of the float32 restatement from its float64 twin on
+# the batches below (rowwise_rel, torch CPU):
+#   encoding forward   4.9e-05 (x = d^2), 4.1e-06 (x = d)
+#   encoding reverse   2.1e-03 / 2.9e-03 interleaved (x = d^2), 4.2e-04 / 5.9e-04 (x = d): x_bar = sum_k s_k (g_sin cos -
+#                      g_cos sin) sums ten terms of size s_0 = 2 pi that cancel to a small row, each carrying the 3e-5 above
+#   edge step x_bar    1.3e-03 with the encoding, 3.0e-04 without (a 128-term dot product with W_c that cancels likewise);
+#                      its forward and h_bar are 8e-07 from float64 and keep the default cap
+ENC_CAP = 2e-4        # forward rows of the encoding: 2 x 4.9e-05, rounded up
+ENC_REV_CAP = 1e-2    # x_bar rows: 2 x 2.9e-03, rounded up
+
+
+def _rag(values, splits):
+    return RaggedTensor.from_numpy(np.ascontiguousarray(values), splits)
+
+
+def _inputs(b, attributes=True):
+    first = b["node_attributes"] if attributes else b["node_number"]
+    out = [_rag(first, b["node_splits"]), _rag(b["node_coordinates"], b["node_splits"]),
+           _rag(b["edge_indices"], b["edge_splits"])]
+    if "edge_attributes" in b:
+        out.append(_rag(b["edge_attributes"], b["edge_splits"]))
+    return out
+
+
+def _shuffled(b, seed=0, stable_by_sender=False):
+    """The same batch with every molecule's edge list reordered (randomly, or stably by the sender column)."""
+    out = dict(b)
+    rng = np.random.default_rng(seed)
+    e, s = b["edge_indices"].copy(), b["edge_splits"]
+    for g in range(len(s) - 1):
+        rows = e[s[g]:s[g + 1]]
+        order = np.argsort(rows[:, 1], kind="stable") if stable_by_sender else rng.permutation(len(rows))
+        e[s[g]:s[g + 1]] = rows[order]
+    out["edge_indices"] = e
+    return out
+
+
+def _norm(b, square=True):
+    """Engine norm output (E, 1) of a batch and its ragged edge index."""
+    _, x, ei = _inputs(b)[:3]
+    with torch.no_grad():
+        p1, p2 = NodePosition()([x, ei])
+        return EuclideanNorm(axis=2, keepdims=True, square_norm=square)(LazySubtract()([p1, p2])), ei
+
+
+def _ref_norm(b, dtype, square=True):
+    ei = torch.from_numpy(ref.flat_edges(b))
+    x = torch.tensor(b["node_coordinates"], dtype=dtype)
+    return ref.edge_norm(x[ei[:, 0]] - x[ei[:, 1]], {"square_norm": square})
+
+
+def _model(cfg, seed=14):
+    m = EGNN.make_model(**cfg)
+    p = list(synth.egnn_params(m, seed=seed).values())
+    m.set_weights(p)
+    return m, p
+
+
+# ------------------------------------------------------------------------------------------------ position encoding
+@pytest.mark.parametrize("interleave", [False, True])
+@pytest.mark.parametrize("square", [True, False])
+def test_position_encoding_and_reverse_rows(interleave, square):
+    b = synth.egnn_batch(sizes=MIXED, seed=3)
+    layer = PositionEncodingBasisLayer(interleave_sin_cos=interleave)
+    x, _ = _norm(b, square)
+    assert float(x.values.max()) > (40.0 if square else 6.0)      # arguments of several hundred radians at x = d^2
+    xv = x.values.detach().clone().requires_grad_(True)
+    with torch.enable_grad():
+        enc = layer(x.with_values(xv)).values
+        g = torch.from_numpy(np.random.default_rng(1).normal(size=tuple(enc.shape)).astype(np.float32)).cuda()
+        (x_bar,) = torch.autograd.grad(enc, [xv], g)
+    with torch.no_grad():
+        plain = layer(x).values
+    assert torch.equal(plain, enc.detach()) and tuple(enc.shape) == (len(b["edge_indices"]), 20)
+    outs = {}
+    for dt in (torch.float32, torch.float64):
+        xr = _ref_norm(b, dt, square).detach().requires_grad_(True)
+        e = ref.position_encoding(xr, dt, interleave=interleave)
+        (gx,) = torch.autograd.grad(e, [xr], g.cpu().to(dt))
+        outs[dt] = (e.detach().numpy(), gx.numpy())
+    what = "position encoding x=%s%s" % ("d^2" if square else "d", " interleaved" if interleave else "")
+    assert_rows_close(enc.detach().cpu().numpy(), outs[torch.float32][0], outs[torch.float64][0], what=what, cap=ENC_CAP)
+    assert_rows_close(x_bar.cpu().numpy(), outs[torch.float32][1], outs[torch.float64][1], what=what + " reverse",
+                      cap=ENC_REV_CAP)
+
+
+def test_position_encoding_c_abi_guards():
+    lib = _ffi.lib()
+    assert lib.mp_position_encoding_f32(None, 0, None, 10, 0, None, None) == _ffi.MP_OK
+    assert lib.mp_position_encoding_f32(None, 4, None, 10, 0, None, None) == _ffi.MP_EINVAL
+    assert lib.mp_position_encoding_grad_f32(None, -1, None, 10, 0, None, None, None) == _ffi.MP_EINVAL
+    # the fused step takes encodings of at most 64 columns
+    assert lib.mp_egnn_edge_f32(None, None, 4, None, None, 0, None, None, None, 33, 0, None, None, 4, None, None, 4, None,
+                                None, 5, 0.05, None, 0, None, None, None, None) == _ffi.MP_EINVAL
+    assert lib.mp_egnn_edge_f32(None, None, 0, None, None, 0, None, None, None, 10, 0, None, None, 4, None, None, 4, None,
+                                None, 5, 0.05, None, 0, None, None, None, None) == _ffi.MP_OK
+    assert lib.mp_egnn_edge_grad_f32(None, 4, None, None, 0, None, None, None, 10, 0, None, 4, None, 4, None, None, 5,
+                                     0.05, None, None, None) == _ffi.MP_OK
+
+
+# ------------------------------------------------------------------------------------------------ fused edge step
+def _edge_layers(attention, encoding, seed=5):
+    rng = np.random.default_rng(seed)
+    edge_mlp = GraphMLP(units=[128, 128], activation=["swish", "swish"])
+    att = GraphMLP(units=1, activation="sigmoid") if attention else None
+    enc = PositionEncodingBasisLayer() if encoding else None
+    edge_mlp.ensure_built((None, None, 256 + (20 if encoding else 1)))
+    if att is not None:
+        att.ensure_built((None, None, 128))
+    for mlp in (edge_mlp, att):
+        if mlp is not None:
+            mlp.set_weights([synth.glorot_uniform(rng, w.shape[0], w.shape[-1], shape=w.shape) if w.ndim == 2 else
+                             rng.uniform(-0.1, 0.1, size=w.shape).astype(np.float32) for w in mlp.get_weights()])
+    return FusedEdgeStep(edge_mlp, att, enc)
+
+
+def _sequence(step, h, x, ei):
+    """The reference's layer sequence of the edge step (EGNN.py:151-174) on the same layers."""
+    if step.encoding is not None:
+        x = step.encoding(x)
+    h_i, h_j = GatherEmbeddingSelection([0, 1])([h, ei])
+    m = step.edge_mlp(LazyConcatenate()([h_i, h_j, x]))
+    if step.attention_mlp is not None:
+        m = LazyMultiply()([step.attention_mlp(m), m])
+    return PoolingLocalEdges(pooling_method="sum")([h, m, ei])
+
+
+def _mlp_weights(mlp, dtype):
+    if mlp is None:
+        return None
+    w = [torch.tensor(a, dtype=dtype) for a in mlp.get_weights()]
+    acts = [a.activation for a in mlp.mlp_activation_layer_list]
+    return [(w[2 * i], w[2 * i + 1], acts[i]) for i in range(len(acts))]
+
+
+def _edge_case(b, attention, encoding, seed=6):
+    rng = np.random.default_rng(seed)
+    x, ei = _norm(b)
+    n = len(b["node_coordinates"])
+    h = _rag(rng.normal(size=(n, 128)).astype(np.float32), b["node_splits"])
+    return _edge_layers(attention, encoding), h, x, ei
+
+
+@pytest.mark.parametrize("attention", [True, False])
+@pytest.mark.parametrize("encoding", [True, False])
+@pytest.mark.parametrize("order", ["sorted", "shuffled"])
+def test_fused_edge_step_forward_and_reverse(attention, encoding, order):
+    b = synth.egnn_batch(sizes=MIXED, seed=7)
+    if order == "shuffled":
+        b = _shuffled(b, seed=2)
+    step, h, x, ei = _edge_case(b, attention, encoding)
+    hv = h.values.detach().clone().requires_grad_(True)
+    xv = x.values.detach().clone().requires_grad_(True)
+    g = torch.from_numpy(np.random.default_rng(8).normal(size=(int(hv.shape[0]), 128)).astype(np.float32)).cuda()
+    with torch.enable_grad():
+        fused = step(h.with_values(hv), x.with_values(xv), ei).values
+        fh, fx = torch.autograd.grad(fused, [hv, xv], g)
+        seq = _sequence(step, h.with_values(hv), x.with_values(xv), ei).values
+        sh, sx = torch.autograd.grad(seq, [hv, xv], g)
+    with torch.no_grad():
+        plain = step(h, x, ei).values
+    assert torch.equal(plain, fused.detach())      # saving the pre-activations does not change the result
+    ei_flat = torch.from_numpy(ref.flat_edges(b))
+    outs = {}
+    for dt in (torch.float32, torch.float64):
+        hr = hv.detach().cpu().to(dt).requires_grad_(True)
+        xr = xv.detach().cpu().to(dt).requires_grad_(True)
+        _, m_i = ref.edge_step(hr, xr, ei_flat, _mlp_weights(step.edge_mlp, dt), _mlp_weights(step.attention_mlp, dt),
+                               dt, expand=encoding)
+        gh, gx = torch.autograd.grad(m_i, [hr, xr], g.cpu().to(dt))
+        outs[dt] = (m_i.detach().numpy(), gh.numpy(), gx.numpy())
+    what = "edge step att=%d enc=%d %s" % (attention, encoding, order)
+    for k, name, got, other in ((0, "forward", fused, seq), (1, "h_bar", fh, sh), (2, "x_bar", fx, sx)):
+        got, other = got.detach().cpu().numpy(), other.detach().cpu().numpy()
+        r32, r64 = outs[torch.float32][k], outs[torch.float64][k]
+        cap = ENC_REV_CAP if name == "x_bar" else 5e-5
+        assert_rows_close(got, r32, r64, what="%s %s" % (what, name), cap=cap)
+        # the layer sequence is the same float32 function in another summation order: same budget
+        assert_rows_close(other, r32, r64, what="%s %s (layer sequence)" % (what, name), cap=cap)
+        bar = max(1e-5, min(2 * rowwise_rel(r32, r64), cap))
+        assert rowwise_rel(got, other) <= 2 * bar, "%s %s: fused vs layer sequence %.3g (bar %.3g)" % (
+            what, name, rowwise_rel(got, other), 2 * bar)
+    ns = b["node_splits"]
+    assert torch.all(fused[ns[1]:ns[2]] == 0)       # the lone atom: a node without edges
+
+
+def test_fused_edge_step_isolated_nodes_and_reorders():
+    # a short cutoff leaves atoms without neighbours inside molecules; the tile walk must give them zero rows
+    b = synth.egnn_batch(num_graphs=6, seed=9, min_distance=0.9, max_distance=1.5)
+    deg = np.bincount(ref.flat_edges(b)[:, 0], minlength=len(b["node_coordinates"]))
+    assert np.any(deg == 0) and np.any(deg > 0)
+    step, h, x, ei = _edge_case(b, True, True)
+    with torch.no_grad():
+        out = step(h, x, ei).values
+        seq = _sequence(step, h, x, ei).values
+    assert torch.all(out[torch.from_numpy(deg == 0).cuda()] == 0)
+    assert_rows_close(out.cpu().numpy(), seq.cpu().numpy(), what="edge step, isolated atoms")
+    # a stable reorder by the sender column keeps every receiver's list order: identical bits
+    b = synth.egnn_batch(num_graphs=4, seed=10)
+    step, h, x, ei = _edge_case(b, True, True)
+    b2 = _shuffled(b, stable_by_sender=True)
+    assert not np.array_equal(b2["edge_indices"], b["edge_indices"])
+    x2, ei2 = _norm(b2)
+    with torch.no_grad():
+        base = step(h, x, ei).values
+        again = step(h, x2, ei2).values
+    assert torch.equal(base, again)
+
+
+def test_fused_edge_step_is_deterministic_across_runs_and_streams():
+    b = synth.egnn_batch(num_graphs=16, seed=11)
+    step, h, x, ei = _edge_case(b, True, True)
+    hv = h.values.detach().clone().requires_grad_(True)
+
+    def run():
+        with torch.enable_grad():
+            out = step(h.with_values(hv), x, ei).values
+            (gh,) = torch.autograd.grad(out.sum(), [hv])
+        return out.detach(), gh
+
+    o1, g1 = run()
+    o2, g2 = run()
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        o3, g3 = run()
+    s.synchronize()
+    assert torch.equal(o1, o2) and torch.equal(o1, o3) and torch.equal(g1, g2) and torch.equal(g1, g3)
+
+
+# ------------------------------------------------------------------------------------------------ model
+def _default_batch(num_graphs, seed):
+    b = synth.egnn_batch(num_graphs=num_graphs, seed=seed, max_distance=5.0)
+    b["edge_attributes"] = np.random.default_rng(seed + 1).normal(size=(len(b["edge_indices"]), 10)).astype(np.float32)
+    return b
+
+
+@pytest.mark.parametrize("which", ["md17", "qm9", "default"])
+def test_model_matches_restatement_64_molecules(which):
+    if which == "default":
+        cfg, b = {}, _default_batch(64, 12)
+    else:
+        cfg, b = (synth.EGNN_MD17 if which == "md17" else synth.EGNN_QM9), synth.egnn_batch(num_graphs=64, seed=12)
+    m, p = _model(cfg)
+    assert m.fused_edge_blocks == ([False] * 4 if which == "default" else [True] * 7)
+    x = _inputs(b, attributes=which != "default")
+    with torch.no_grad():
+        got = m(x).cpu().numpy()
+        m.use_fused_edge = False
+        seq = m(x).cpu().numpy()
+        m.use_fused_edge = True
+    r32 = ref.egnn_forward(p, b, m.config, dtype=torch.float32).detach().numpy()
+    r64 = ref.egnn_forward(p, b, m.config, dtype=torch.float64).detach().numpy()
+    assert got.shape == r64.shape == (64, 1)
+    assert_rows_close(got, r32, r64, what="EGNN %s" % which)
+    # the layer sequence: no further from float64 than a float32 pipeline is (assert_rows_close's first condition)
+    e_seq, e_32 = rowwise_rel(seq, r64), rowwise_rel(r32, r64)
+    print("[parity] EGNN %s layer sequence: %.2e from float64, float32 restatement %.2e" % (which, e_seq, e_32))
+    assert e_seq <= max(4 * e_32, 2e-6)
+    if which == "default":
+        assert np.array_equal(got, seq)
+
+
+def test_node_output_embedding():
+    cfg = dict(synth.EGNN_MD17, output_embedding="node")
+    b = synth.egnn_batch(num_graphs=8, seed=13)
+    m, p = _model(cfg)
+    with torch.no_grad():
+        got = m(_inputs(b)).cpu().numpy()
+    assert got.shape == (8, 21, 1)
+    r32 = ref.egnn_forward(p, b, m.config, dtype=torch.float32).detach().numpy()
+    r64 = ref.egnn_forward(p, b, m.config, dtype=torch.float64).detach().numpy()
+    assert_rows_close(got.reshape(-1, 1), r32, r64, what="EGNN node embedding")
+
+
+def _force_model(cfg=None):
+    m, p = _model(synth.EGNN_MD17 if cfg is None else cfg)
+    efm = EnergyForceModel(model_energy=m, coordinate_input=1, output_to_tensor=False, output_squeeze_states=True)
+    return efm, m, p
+
+
+def test_forces_through_energy_force_model():
+    # cutoff 6 A: at 10 A the float32 restatement's own worst molecule is 2.7e-05 (seed 15) to 6.3e-05 (seed 16) of its
+    # force scale from float64 (the sin arguments above), at or over the 5e-5 cap of assert_forces_close; here 1.1e-05
+    b = synth.egnn_batch(sizes=[1, 2] + [21] * 14, seed=16, max_distance=6.0)
+    efm, m, p = _force_model()
+    eng, force = efm(_inputs(b))
+    e, f = eng.cpu().numpy(), force.values.cpu().numpy()
+    e64, f64 = ref.energy_forces(p, b, m.config, dtype=torch.float64)
+    e32, f32 = ref.energy_forces(p, b, m.config, dtype=torch.float32)
+    assert_rows_close(e.reshape(-1, 1), e32.numpy(), e64.numpy(), what="EnergyForceModel energy")
+    assert_forces_close(f, f32.numpy(), f64.numpy(), b["node_splits"], what="EGNN forces")
+    m.use_fused_edge = False
+    eng_s, force_s = efm(_inputs(b))
+    m.use_fused_edge = True
+    assert_forces_close(force_s.values.cpu().numpy(), f32.numpy(), f64.numpy(), b["node_splits"],
+                        what="EGNN forces, layer sequence")
+    assert_rows_close(eng_s.cpu().numpy().reshape(-1, 1), e32.numpy(), e64.numpy(), what="energy, layer sequence")
+    # no net force on any molecule; the lone atom feels none
+    ns, scale = b["node_splits"], float(np.max(np.abs(f64.numpy())))
+    for g in range(len(ns) - 1):
+        assert np.max(np.abs(f[ns[g]:ns[g + 1]].sum(axis=0))) <= 1e-4 * scale, g
+    assert np.all(f[0] == 0)
+
+
+def test_forces_at_model_default_flow_through_the_coordinate_updates():
+    b = _default_batch(8, 16)
+    efm, m, p = _force_model({})
+    eng, force = efm(_inputs(b, attributes=False))
+    e64, f64 = ref.energy_forces(p, b, m.config, dtype=torch.float64)
+    e32, f32 = ref.energy_forces(p, b, m.config, dtype=torch.float32)
+    assert float(f64.abs().max()) > 0
+    assert_rows_close(eng.cpu().numpy().reshape(-1, 1), e32.numpy(), e64.numpy(), what="model_default energy")
+    assert_forces_close(force.values.cpu().numpy(), f32.numpy(), f64.numpy(), b["node_splits"],
+                        what="EGNN model_default forces")
+
+
+def test_rotation_translation_invariance():
+    b = synth.egnn_batch(num_graphs=8, seed=17)
+    efm, _, _ = _force_model()
+    base = efm(_inputs(b))
+    q, _ = np.linalg.qr(np.random.default_rng(18).normal(size=(3, 3)))
+    b2 = dict(b)
+    b2["node_coordinates"] = (b["node_coordinates"].astype(np.float64) @ q.T + np.array([0.7, -1.3, 2.1])).astype(
+        np.float32)
+    rot = efm(_inputs(b2))
+    e0, e1 = base[0].cpu().numpy(), rot[0].cpu().numpy()
+    f0, f1 = base[1].values.cpu().numpy(), rot[1].values.cpu().numpy()
+    assert np.max(np.abs(e1 - e0)) <= 1e-4 * max(1.0, np.max(np.abs(e0)))
+    assert np.max(np.abs(f1 - f0 @ q.T)) <= 1e-3 * np.max(np.abs(f0))
+
+
+def test_replay_and_determinism_of_the_model():
+    b = synth.egnn_batch(num_graphs=16, seed=19)
+    m, _ = _model(synth.EGNN_MD17)
+    x = _inputs(b)
+    with torch.no_grad():
+        first = m(x)
+        assert m.last_route == "eager"
+        second = m(x)
+        third = m(x)
+        assert m.last_route == "graph"
+    assert torch.equal(first, second) and torch.equal(first, third)
+    # weights changed in place: the replayed graph reads them where they are (the fused step keeps no repacked copy)
+    m.set_weights([0.5 * w for w in m.get_weights()])
+    with torch.no_grad():
+        replayed = m(x)
+        assert m.last_route == "graph"
+        m.auto_graph = False
+        eager = m(x)
+        m.auto_graph = True
+    assert torch.equal(replayed, eager) and not torch.equal(replayed, first)
+    # the switch drops the captured graphs: the next call runs the layer sequence, not a replay of the fused route
+    m.use_fused_edge = False
+    with torch.no_grad():
+        seq = m(x)
+    assert m.last_route == "eager"
+    m.use_fused_edge = True
+    assert_rows_close(seq.cpu().numpy(), eager.cpu().numpy(), what="layer sequence after the switch")
+    efm = EnergyForceModel(model_energy=m, coordinate_input=1, output_to_tensor=False, output_squeeze_states=True)
+    f1, f2 = efm(x)[1].values, efm(x)[1].values
+    assert torch.equal(f1, f2)
+
+
+# ------------------------------------------------------------------------------------------------ training
+def test_energy_sgd_trajectory_matches_restatement():
+    b = synth.egnn_batch(num_graphs=8, seed=20)
+    m, p = _model(synth.EGNN_MD17)
+    x = _inputs(b)
+    with torch.no_grad():
+        before = m(x).clone()
+    target = np.random.default_rng(4).normal(size=(8, 1)).astype(np.float32)
+    # energies of the random model are ~3e3 (sum pooling): lr 1e-6 keeps the three steps a descent; the float32
+    # restatement's own trajectory is 6e-07 from the float64 one (losses) and 2e-07 (weights)
+    m.compile(optimizer=torch.optim.SGD(m.trainable_weights, lr=1e-6), loss="mean_absolute_error")
+    losses = [m.train_on_batch(x, target) for _ in range(3)]
+    assert not any(t.requires_grad for t in m.trainable_weights)
+    w = [torch.tensor(a, dtype=torch.float64, requires_grad=True) for a in p]
+    opt = torch.optim.SGD(w, lr=1e-6)
+    ref_losses = []
+    for _ in range(3):
+        opt.zero_grad()
+        loss = (ref.egnn_forward(w, b, m.config) - torch.from_numpy(target).double()).abs().mean()
+        loss.backward()
+        opt.step()
+        ref_losses.append(float(loss.detach()))
+    print("[training] engine %s restatement %s" % (losses, ref_losses))
+    np.testing.assert_allclose(losses, ref_losses, rtol=1e-5)
+    moved = [float(np.max(np.abs(a - c))) for a, c in zip(m.get_weights(), p)]
+    assert max(moved) > 0
+    for t, a, start, step in zip(w, m.get_weights(), p, moved):
+        r = t.detach().numpy()
+        scale = max(float(np.max(np.abs(r))), 1e-3)
+        assert np.max(np.abs(a - r)) <= 1e-5 * scale
+        # every tensor the float64 trajectory moves by more than float32 resolution moves on the engine (the last
+        # block's attention gate of this random model is shut, its edge weights get no gradient in either)
+        if np.max(np.abs(r - start)) > 1e-5 * scale:
+            assert step > 0
+    # the fused route serves the trained weights
+    with torch.no_grad():
+        after = m(x)
+        m.use_fused_edge = False
+        seq = m(x)
+        m.use_fused_edge = True
+    assert not torch.equal(after, before)
+    r64 = ref.egnn_forward([t.detach() for t in w], b, m.config).numpy()
+    r32 = ref.egnn_forward([t.detach() for t in w], b, m.config, dtype=torch.float32).numpy()
+    assert_rows_close(after.cpu().numpy(), r32, r64, what="trained weights, fused")
+    assert_rows_close(seq.cpu().numpy(), r32, r64, what="trained weights, layer sequence")
+
+
+# ------------------------------------------------------------------------------------------------ guards
+def test_force_training_and_create_graph_raise():
+    b = synth.egnn_batch(num_graphs=2, seed=21)
+    efm, m, _ = _force_model()
+    efm.compile(optimizer="sgd", loss=["mean_squared_error", "mean_squared_error"])
+    with pytest.raises(NotImplementedError):
+        efm.train_on_batch(_inputs(b), [np.zeros((2, 1), np.float32), np.zeros((42, 3), np.float32)])
+    assert not any(t.requires_grad for t in m.trainable_weights)
+    x, ei = _norm(b)
+    xv = x.values.detach().clone().requires_grad_(True)
+    with torch.enable_grad():
+        enc = PositionEncodingBasisLayer()(x.with_values(xv)).values
+        with pytest.raises(NotImplementedError, match="PositionEncodingBasisLayer"):
+            torch.autograd.grad(enc.sum(), [xv], create_graph=True)
+    step, h, x, ei = _edge_case(b, True, True)
+    hv = h.values.detach().clone().requires_grad_(True)
+    with torch.enable_grad():
+        out = step(h.with_values(hv), x, ei).values
+        with pytest.raises(NotImplementedError, match="edge step"):
+            torch.autograd.grad(out.sum(), [hv], create_graph=True)
+    # trainable edge weights in grad mode: the fused rule has no gradients for them, the model steps aside
+    assert step.weights_need_grad() is False
+    for t in step.weight_tensors():
+        t.requires_grad_(True)
+    try:
+        with torch.enable_grad():
+            assert step.weights_need_grad() is True
+        with torch.no_grad():
+            assert step.weights_need_grad() is False
+    finally:
+        for t in step.weight_tensors():
+            t.requires_grad_(False)
