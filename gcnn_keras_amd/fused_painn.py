@@ -135,6 +135,9 @@ def message_tile_table(node_splits, ptr, basis, per=None, lds_limit=160 * 1024, 
     table[:, 0], table[:, 1], table[:, 2], table[:, 3] = r_lo, r_hi, ns[graph], ns[graph + 1]
     table[:, 4], table[:, 5] = ptr[r_lo], ptr[r_hi]
     max_rows, max_edges = int(sizes.max()), int((table[:, 5] - table[:, 4]).max())
+    # sizes the probes refuse outright (csrc/mp_painn_fused.hip: "tile far beyond LDS"): no table, the gather kernels serve
+    if max_rows > 4096 or max_edges > (1 << 20):
+        return None
     lds = ctypes.c_size_t(0)
     max_own = int((r_hi - r_lo).max())
     if reverse:

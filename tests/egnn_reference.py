@@ -10,6 +10,9 @@ import torch
 ACTIVATIONS = {
     None: lambda x: x, "linear": lambda x: x, "swish": lambda x: x * torch.sigmoid(x), "sigmoid": torch.sigmoid,
     "tanh": torch.tanh, "relu": torch.relu, "softplus": torch.nn.functional.softplus,
+    "shifted_softplus": lambda x: torch.nn.functional.softplus(x) - float(np.log(2.0)),
+    "leaky_relu": lambda x: torch.where(x >= 0, x, 0.05 * x),      # the slope layers/modules.py dense_values passes
+    "selu": torch.selu,
 }
 
 

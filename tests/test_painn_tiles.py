@@ -40,3 +40,15 @@ def test_tile_table_refuses_what_does_not_fit_lds_and_handles_empty_graphs():
     assert message_tile_table(big, np.zeros(81, np.int32), 20) is None
     assert message_tile_table(np.array([0, 0]), np.zeros(1, np.int32), 20) is None
     assert message_tile_table(b["node_splits"], _csr(b), 32) is None          # no free bias slot
+
+
+def test_tile_table_is_none_beyond_the_sizes_the_lds_probe_takes():
+    """A graph of more than 4096 nodes or a tile of more than 2^20 edges: the probes of csrc/mp_painn_fused.hip refuse such
+    sizes outright; the table must be None (``FusedPainn.bind`` then runs the gather kernels), not an exception."""
+    for reverse in (False, True):
+        assert message_tile_table([0, 4096], np.arange(4097) * 10, 20, reverse=reverse) is None       # asked, does not fit
+        assert message_tile_table([0, 4097], np.arange(4098) * 10, 20, reverse=reverse) is None
+        assert message_tile_table([0, 4], np.arange(5) * 600000, 20, reverse=reverse) is None
+        assert message_tile_table([0, 62], np.arange(63) * 20000, 20, per=62, reverse=reverse) is None
+        # a large graph next to small ones: still no table (one workgroup stages a whole graph's rows)
+        assert message_tile_table([0, 5, 5005, 5010], np.arange(5011) * 12, 20, reverse=reverse) is None
