@@ -103,12 +103,8 @@ _SIGNATURES = {
     "mp_painn_message_bwd_tiles_lds_bytes": [c_int, c_int, c_int, c_int, c_int, P],
     "mp_painn_message_bwd_tiles_f32": [P, P, c_int64, P, P, c_int, P, P, P, P, P, P, P, c_int64, P, c_int, c_int, c_int,
                                        c_int, P, P, P, P, P, P, c_int, P],
-    "mp_painn_update_pre_f32": [P, P, c_int64, P, P, P],
     "mp_painn_update_fused_f32": [P, P, P, c_int64, P, P, c_int, c_float, P, P, P, P, P, P, P, P, P],
     "mp_painn_update_fused_bwd_f32": [P, P, P, P, P, P, c_int64, P, c_int, c_float, P, P, P, P, P],
-    "mp_painn_update_post_f32": [P, P, P, P, P, c_int64, P, P, P],
-    "mp_painn_update_post_bwd_f32": [P, P, P, P, P, c_int64, P, P, P],
-    "mp_painn_update_pre_bwd_f32": [P, P, P, P, P, P, P, c_int64, P, P, P],
     "mp_edge_geometry_bwd_f32": [P, P, c_int, P, P, P, P, P, P, c_int64, c_int64, c_float, P, P],
     "mp_schnet_node_pack_f32": [P, c_int, c_int, P, P],
     "mp_schnet_node_pack_bf16_f32": [P, c_int, c_int, P, P],
@@ -374,6 +370,14 @@ def call(name, *args):
             _roctx.roctxRangePop()
         return
     check(getattr(lib(), name)(*args))
+
+
+def workspace_bytes(name, *args):
+    """Size in bytes that the query entry point ``name`` (``mp_*_ws_bytes`` / ``mp_*_workspace_bytes``) reports for
+    ``args``: one engine call, its ``size_t*`` result as an int."""
+    nbytes = c_size_t(0)
+    call(name, *args, ctypes.byref(nbytes))
+    return nbytes.value
 
 
 if os.environ.get("MPENGINE_ROCTX") == "1":

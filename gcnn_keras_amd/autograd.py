@@ -210,17 +210,15 @@ class PoolGraphAdjoint(torch.autograd.Function):
 
 def dense_wgrad(x, g, with_bias=True):
     """``(x^T g, sum_r g)`` over the rows of ``x`` (..., K) and ``g`` (..., U) on ``mp_dense_wgrad_f32``."""
-    import ctypes
     k, u = int(x.shape[-1]), int(g.shape[-1])
     xc, gc = x.contiguous(), g.contiguous()
     rows = xc.numel() // max(k, 1)
     dw = torch.empty((k, u), dtype=torch.float32, device=g.device)
     db = torch.empty((u,), dtype=torch.float32, device=g.device) if with_bias else None
-    nbytes = ctypes.c_size_t(0)
-    _ffi.call("mp_dense_wgrad_ws_bytes", rows, k, u, ctypes.byref(nbytes))
-    ws = torch.empty((max(nbytes.value, 4) // 4,), dtype=torch.float32, device=g.device) if nbytes.value else None
+    nbytes = _ffi.workspace_bytes("mp_dense_wgrad_ws_bytes", rows, k, u)
+    ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.float32, device=g.device) if nbytes else None
     _ffi.call("mp_dense_wgrad_f32", _ffi.ptr(xc), rows, k, _ffi.ptr(gc), u, _ffi.ptr(dw), _ffi.ptr(db), _ffi.ptr(ws),
-              nbytes.value, _ffi.stream())
+              nbytes, _ffi.stream())
     return dw, db
 
 
@@ -253,8 +251,8 @@ class Dense(torch.autograd.Function):
             gx, gw, gb = DenseAdjoint.apply(g, ctx.x, ctx.kernel, ctx.bias, ctx.pre, ctx.act, ctx.alpha, want_x, want_w,
                                             want_b)
             return gx, gw, gb, None, None
-        gx, gw, gb, _ = _dense_backward(g.contiguous(), ctx.x, ctx.kernel, ctx.pre, ctx.act, ctx.alpha, want_x, want_w,
-                                        want_b)
+        gx, gw, gb, _ = _affine_backward(_dense_ops(), g.contiguous(), ctx.x, ctx.kernel, ctx.pre, ctx.act, ctx.alpha,
+                                         want_x, want_w, want_b)
         return gx, gw, gb, None, None
 
 
@@ -265,9 +263,44 @@ def _sum_rows(g):
     return out
 
 
-def _dense_backward(gc, x, kernel, pre, act, alpha, want_x, want_w, want_b):
-    """First-order Dense backward: (dx, dW, db, gp) with gp = dy * act'(pre)."""
+def _dense_ops():
+    """The three operations the affine rules below are written in, for Dense: ``affine(x, W, b) = x W (+ b)``,
+    ``affine_t(g, W) = g W^T`` and ``wgrad(x, g, with_kernel, with_bias) = (x^T g, sum_rows g)``."""
     from .layers.modules import _dense_raw
+
+    def affine(x, w, b):
+        return _dense_raw(x, w, b, 0, 0.0)
+
+    def affine_t(g, w):
+        return _dense_raw(g, w.t().contiguous(), None, 0, 0.0)   # (units, in): layout change only
+
+    def wgrad(x, g, with_kernel=True, with_bias=True):
+        if with_kernel:
+            return dense_wgrad(x, g, with_bias=with_bias)
+        return None, _sum_rows(g)
+
+    return affine, affine_t, wgrad
+
+
+def _relational_ops(rel, nrel):
+    """The same three operations with one kernel per relation (``W[rel]``), for RelationalDense."""
+    from .layers.relational import relational_dense_raw, relational_dense_t_raw, relational_wgrad
+
+    def affine(x, w, b):
+        return relational_dense_raw(x, w, b, rel, 0, 0.0)[1]
+
+    def affine_t(g, w):
+        return relational_dense_t_raw(g, w.contiguous(), rel)
+
+    def wgrad(x, g, with_kernel=True, with_bias=True):
+        return relational_wgrad(x, g, rel, nrel, with_kernel=with_kernel, with_bias=with_bias)
+
+    return affine, affine_t, wgrad
+
+
+def _affine_backward(ops, gc, x, kernel, pre, act, alpha, want_x, want_w, want_b):
+    """First-order backward of y = act(x W + b) in the operations ``ops``: (dx, dW, db, gp) with gp = dy * act'(pre)."""
+    _, affine_t, wgrad = ops
     if pre is not None:
         gp = torch.empty_like(gc)
         _ffi.call("mp_activation_grad_f32", act, float(alpha), _ffi.ptr(pre), _ffi.ptr(gc), gc.numel(), _ffi.ptr(gp),
@@ -275,13 +308,58 @@ def _dense_backward(gc, x, kernel, pre, act, alpha, want_x, want_w, want_b):
         gc = gp
     gx = gw = gb = None
     if want_x:
-        wt = kernel.t().contiguous()  # (units, in): layout change only
-        gx = _dense_raw(gc, wt, None, 0, 0.0)
-    if want_w:
-        gw, gb = dense_wgrad(x, gc, with_bias=want_b)
-    elif want_b:
-        gb = _sum_rows(gc)
+        gx = affine_t(gc, kernel)
+    if want_w or want_b:
+        gw, gb = wgrad(x, gc, with_kernel=want_w, with_bias=want_b)
     return gx, gw, gb, gc
+
+
+def _affine_adjoint_backward(ops, ctx, hx, hw, hb):
+    """Reverse of ``_affine_backward`` as an op of (dy, x, W, b): ``(dy_bar, x_bar, W_bar, b_bar)`` for the upstreams
+    hx, hW, hb on dx, dW, db, or None when none of them arrived (the mathematics: ``DenseAdjoint``)."""
+    from .layers.modules import _binary_raw
+    affine, affine_t, wgrad = ops
+    need_g, need_x, need_w, need_b = ctx.needs_input_grad[:4]
+    x, kernel, pre, gp = ctx.x, ctx.kernel, ctx.pre, ctx.gp
+    u = int(kernel.shape[-1])
+    h_gp = None
+    if hx is not None:
+        h_gp = affine(hx.contiguous(), kernel, None)
+    if hw is not None:
+        h_gp = _add(h_gp, affine(x, hw.contiguous(), hb.contiguous() if hb is not None else None))
+    elif hb is not None:
+        rows = gp.numel() // max(u, 1)
+        zero = torch.zeros((rows, u), dtype=torch.float32, device=gp.device)
+        h_gp = _add(h_gp, _binary_raw(_ffi.MP_ADD, zero, hb.contiguous().view(1, u)).view(gp.shape))
+    if h_gp is None:
+        return None
+    g_bar = pre_bar = None
+    if pre is None:
+        g_bar = h_gp if need_g else None      # linear: act'' = 0, no pre-activation term
+    else:
+        if need_g:
+            g_bar = torch.empty_like(h_gp)
+        if need_x or need_w or need_b:
+            pre_bar = torch.empty_like(h_gp)
+        _ffi.call("mp_activation_grad2_f32", ctx.act, float(ctx.alpha), _ffi.ptr(pre), _ffi.ptr(ctx.g),
+                  _ffi.ptr(h_gp), _ffi.ptr(pre_bar), _ffi.ptr(g_bar), h_gp.numel(), _ffi.stream())
+    x_bar = w_bar = b_bar = None
+    if need_x:
+        if hw is not None:
+            x_bar = affine_t(gp, hw)
+        if pre_bar is not None:
+            x_bar = _add(x_bar, affine_t(pre_bar, kernel))
+    if need_w:
+        if hx is not None:
+            w_bar = wgrad(hx, gp, with_bias=False)[0]
+        if pre_bar is not None:
+            w_pre, b_bar = wgrad(x, pre_bar, with_bias=need_b)
+            w_bar = _add(w_bar, w_pre)
+    if need_b and b_bar is None and pre_bar is not None:
+        b_bar = _sum_rows(pre_bar)
+    if not need_b:
+        b_bar = None
+    return g_bar, x_bar, w_bar, b_bar
 
 
 def _add(a, b):
@@ -305,56 +383,15 @@ class DenseAdjoint(torch.autograd.Function):
     def forward(ctx, g, x, kernel, bias, pre, act, alpha, want_x, want_w, want_b):
         ctx.set_materialize_grads(False)   # an output nobody uses (dW, db in the force pass) brings no upstream
         gc = g.contiguous()
-        gx, gw, gb, gp = _dense_backward(gc, x, kernel, pre, act, alpha, want_x, want_w, want_b)
+        gx, gw, gb, gp = _affine_backward(_dense_ops(), gc, x, kernel, pre, act, alpha, want_x, want_w, want_b)
         ctx.g, ctx.x, ctx.kernel, ctx.pre, ctx.gp, ctx.act, ctx.alpha = gc, x, kernel, pre, gp, act, alpha
         return gx, gw, gb
 
     @staticmethod
     @once_differentiable
     def backward(ctx, hx, hw, hb):
-        from .layers.modules import _binary_raw, _dense_raw
-        need_g, need_x, need_w, need_b = ctx.needs_input_grad[:4]
-        x, kernel, pre, gp = ctx.x, ctx.kernel, ctx.pre, ctx.gp
-        u = int(kernel.shape[1])
-        h_gp = None
-        if hx is not None:
-            h_gp = _dense_raw(hx.contiguous(), kernel, None, 0, 0.0)
-        if hw is not None:
-            h_gp = _add(h_gp, _dense_raw(x, hw.contiguous(), hb.contiguous() if hb is not None else None, 0, 0.0))
-        elif hb is not None:
-            rows = gp.numel() // max(u, 1)
-            zero = torch.zeros((rows, u), dtype=torch.float32, device=gp.device)
-            h_gp = _add(h_gp, _binary_raw(_ffi.MP_ADD, zero, hb.contiguous().view(1, u)).view(gp.shape))
-        if h_gp is None:
-            return (None,) * 10
-        g_bar = pre_bar = None
-        if pre is None:
-            g_bar = h_gp if need_g else None
-        else:
-            want_pre = need_x or need_w or need_b
-            if need_g:
-                g_bar = torch.empty_like(h_gp)
-            if want_pre:
-                pre_bar = torch.empty_like(h_gp)
-            _ffi.call("mp_activation_grad2_f32", ctx.act, float(ctx.alpha), _ffi.ptr(pre), _ffi.ptr(ctx.g),
-                      _ffi.ptr(h_gp), _ffi.ptr(pre_bar), _ffi.ptr(g_bar), h_gp.numel(), _ffi.stream())
-        x_bar = w_bar = b_bar = None
-        if need_x:
-            if hw is not None:
-                x_bar = _dense_raw(gp, hw.t().contiguous(), None, 0, 0.0)
-            if pre_bar is not None:
-                x_bar = _add(x_bar, _dense_raw(pre_bar, kernel.t().contiguous(), None, 0, 0.0))
-        if need_w:
-            if hx is not None:
-                w_bar, _ = dense_wgrad(hx, gp, with_bias=False)
-            if pre_bar is not None:
-                w_pre, b_bar = dense_wgrad(x, pre_bar, with_bias=need_b)
-                w_bar = _add(w_bar, w_pre)
-        if need_b and b_bar is None and pre_bar is not None:
-            b_bar = _sum_rows(pre_bar)
-        if not need_b:
-            b_bar = None
-        return g_bar, x_bar, w_bar, b_bar, None, None, None, None, None, None
+        bars = _affine_adjoint_backward(_dense_ops(), ctx, hx, hw, hb)
+        return (None,) * 10 if bars is None else bars + (None,) * 6
 
 
 class Embedding(torch.autograd.Function):
@@ -373,15 +410,13 @@ class Embedding(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        import ctypes
         gc = g.contiguous()
         n = ctx.numbers.numel()
-        nbytes = ctypes.c_size_t(0)
-        _ffi.call("mp_embedding_grad_ws_bytes", n, ctx.vocab, ctypes.byref(nbytes))
-        ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=gc.device)
+        nbytes = _ffi.workspace_bytes("mp_embedding_grad_ws_bytes", n, ctx.vocab)
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=gc.device)
         out = torch.empty((ctx.vocab, ctx.dim), dtype=torch.float32, device=gc.device)
         _ffi.call("mp_embedding_grad_f32", _ffi.ptr(ctx.numbers), n, _ffi.ptr(gc), ctx.vocab, ctx.dim, _ffi.ptr(ws),
-                  nbytes.value, _ffi.ptr(out), _ffi.stream())
+                  nbytes, _ffi.ptr(out), _ffi.stream())
         return None, out
 
 
@@ -792,22 +827,6 @@ class ACSFAdjoint(torch.autograd.Function):
         return None, g_bar, None
 
 
-def _relational_backward(gc, x, kernel, rel, pre, act, alpha, want_x, want_w, want_b):
-    """First-order RelationalDense backward: (dx, dW, db, gp) with gp = dy * act'(pre)."""
-    from .layers.relational import relational_dense_t_raw, relational_wgrad
-    if pre is not None:
-        gp = torch.empty_like(gc)
-        _ffi.call("mp_activation_grad_f32", act, float(alpha), _ffi.ptr(pre), _ffi.ptr(gc), gc.numel(), _ffi.ptr(gp),
-                  _ffi.stream())
-        gc = gp
-    gx = gw = gb = None
-    if want_x:
-        gx = relational_dense_t_raw(gc, kernel, rel)
-    if want_w or want_b:
-        gw, gb = relational_wgrad(x, gc, rel, int(kernel.shape[0]), with_kernel=want_w, with_bias=want_b)
-    return gx, gw, gb, gc
-
-
 class RelationalDense(torch.autograd.Function):
     """y = act(x W[rel] + b) (mp_relational_dense_f32); backward gp = dy * act'(pre), dx = gp W[rel]^T,
     dW[q] = x_q^T gp_q, db = sum gp, each only when asked.  In grad mode the backward is ``RelationalDenseAdjoint``."""
@@ -829,8 +848,8 @@ class RelationalDense(torch.autograd.Function):
             gx, gw, gb = RelationalDenseAdjoint.apply(g, ctx.x, ctx.kernel, ctx.bias, ctx.rel, ctx.pre, ctx.act,
                                                       ctx.alpha, want_x, want_w, want_b)
             return gx, gw, gb, None, None, None
-        gx, gw, gb, _ = _relational_backward(g.contiguous(), ctx.x, ctx.kernel, ctx.rel, ctx.pre, ctx.act, ctx.alpha,
-                                             want_x, want_w, want_b)
+        gx, gw, gb, _ = _affine_backward(_relational_ops(ctx.rel, int(ctx.kernel.shape[0])), g.contiguous(), ctx.x,
+                                         ctx.kernel, ctx.pre, ctx.act, ctx.alpha, want_x, want_w, want_b)
         return gx, gw, gb, None, None, None
 
 
@@ -843,57 +862,16 @@ class RelationalDenseAdjoint(torch.autograd.Function):
     def forward(ctx, g, x, kernel, bias, rel, pre, act, alpha, want_x, want_w, want_b):
         ctx.set_materialize_grads(False)
         gc = g.contiguous()
-        gx, gw, gb, gp = _relational_backward(gc, x, kernel, rel, pre, act, alpha, want_x, want_w, want_b)
+        gx, gw, gb, gp = _affine_backward(_relational_ops(rel, int(kernel.shape[0])), gc, x, kernel, pre, act, alpha,
+                                          want_x, want_w, want_b)
         ctx.g, ctx.x, ctx.kernel, ctx.rel, ctx.pre, ctx.gp, ctx.act, ctx.alpha = gc, x, kernel, rel, pre, gp, act, alpha
         return gx, gw, gb
 
     @staticmethod
     @once_differentiable
     def backward(ctx, hx, hw, hb):
-        from .layers.modules import _binary_raw
-        from .layers.relational import relational_dense_raw, relational_dense_t_raw, relational_wgrad
-        need_g, need_x, need_w, need_b = ctx.needs_input_grad[:4]
-        x, kernel, rel, pre, gp = ctx.x, ctx.kernel, ctx.rel, ctx.pre, ctx.gp
-        nrel, u = int(kernel.shape[0]), int(kernel.shape[2])
-        h_gp = None
-        if hx is not None:
-            h_gp = relational_dense_raw(hx.contiguous(), kernel, None, rel, 0, 0.0)[1]
-        if hw is not None:
-            h_gp = _add(h_gp, relational_dense_raw(x, hw.contiguous(), hb.contiguous() if hb is not None else None,
-                                                   rel, 0, 0.0)[1])
-        elif hb is not None:
-            rows = gp.numel() // max(u, 1)
-            zero = torch.zeros((rows, u), dtype=torch.float32, device=gp.device)
-            h_gp = _add(h_gp, _binary_raw(_ffi.MP_ADD, zero, hb.contiguous().view(1, u)).view(gp.shape))
-        if h_gp is None:
-            return (None,) * 11
-        g_bar = pre_bar = None
-        if pre is None:
-            g_bar = h_gp if need_g else None      # linear: act'' = 0, no pre-activation term
-        else:
-            if need_g:
-                g_bar = torch.empty_like(h_gp)
-            if need_x or need_w or need_b:
-                pre_bar = torch.empty_like(h_gp)
-            _ffi.call("mp_activation_grad2_f32", ctx.act, float(ctx.alpha), _ffi.ptr(pre), _ffi.ptr(ctx.g),
-                      _ffi.ptr(h_gp), _ffi.ptr(pre_bar), _ffi.ptr(g_bar), h_gp.numel(), _ffi.stream())
-        x_bar = w_bar = b_bar = None
-        if need_x:
-            if hw is not None:
-                x_bar = relational_dense_t_raw(gp, hw.contiguous(), rel)
-            if pre_bar is not None:
-                x_bar = _add(x_bar, relational_dense_t_raw(pre_bar, kernel, rel))
-        if need_w:
-            if hx is not None:
-                w_bar = relational_wgrad(hx, gp, rel, nrel, with_bias=False)[0]
-            if pre_bar is not None:
-                w_pre, b_bar = relational_wgrad(x, pre_bar, rel, nrel, with_bias=need_b)
-                w_bar = _add(w_bar, w_pre)
-        if need_b and b_bar is None and pre_bar is not None:
-            b_bar = _sum_rows(pre_bar)
-        if not need_b:
-            b_bar = None
-        return g_bar, x_bar, w_bar, b_bar, None, None, None, None, None, None, None
+        bars = _affine_adjoint_backward(_relational_ops(ctx.rel, int(ctx.kernel.shape[0])), ctx, hx, hw, hb)
+        return (None,) * 11 if bars is None else bars + (None,) * 7
 
 
 # ------------------------------------------------------------------------------------------------ HDNNP4th

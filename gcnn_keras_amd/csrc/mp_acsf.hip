@@ -62,11 +62,6 @@ __device__ __forceinline__ float dfc_of(float r, float rc) {
   return -0.5f * sinf(r * kPi / rc) * (kPi / rc);
 }
 
-__device__ __forceinline__ float bcast(float v, int s) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), s));
-}
-__device__ __forceinline__ int bcast(int v, int s) { return __builtin_amdgcn_readlane(v, s); }
-
 // relation of entry e and its neighbour indices; -1 when an endpoint is out of range or unmapped
 template <bool G4>
 __device__ __forceinline__ int entry_rel(const AcsfArgs& a, int64_t e, int& j, int& k) {
@@ -161,14 +156,14 @@ __global__ __launch_bounds__(64) void acsf_rows_kernel(AcsfArgs a) {
     }
     const int cnt = min(64, end - base);
     for (int s = 0; s < cnt; ++s) {
-      const int r = bcast(rel, s);
+      const int r = mp_bcast(rel, s);
       if (r < 0) continue;
-      const float Rij = bcast(rij, s), Rc0 = bcast(rc0, s), Fij0 = bcast(fij, s);
-      const float Rik = G4 ? bcast(rik, s) : 0.f, Rjk = G4 ? bcast(rjk, s) : 0.f, Cs = G4 ? bcast(cs, s) : 0.f;
-      const float Fik0 = G4 ? bcast(fik, s) : 0.f, Fjk0 = G4 ? bcast(fjk, s) : 0.f;
-      const float dRij = JVP ? bcast(drij, s) : 0.f;
-      const float dRik = (JVP && G4) ? bcast(drik, s) : 0.f, dRjk = (JVP && G4) ? bcast(drjk, s) : 0.f;
-      const float dCs = (JVP && G4) ? bcast(dcs, s) : 0.f;
+      const float Rij = mp_bcast(rij, s), Rc0 = mp_bcast(rc0, s), Fij0 = mp_bcast(fij, s);
+      const float Rik = G4 ? mp_bcast(rik, s) : 0.f, Rjk = G4 ? mp_bcast(rjk, s) : 0.f, Cs = G4 ? mp_bcast(cs, s) : 0.f;
+      const float Fik0 = G4 ? mp_bcast(fik, s) : 0.f, Fjk0 = G4 ? mp_bcast(fjk, s) : 0.f;
+      const float dRij = JVP ? mp_bcast(drij, s) : 0.f;
+      const float dRik = (JVP && G4) ? mp_bcast(drik, s) : 0.f, dRjk = (JVP && G4) ? mp_bcast(drjk, s) : 0.f;
+      const float dCs = (JVP && G4) ? mp_bcast(dcs, s) : 0.f;
       const float* prow = par + static_cast<int64_t>(crow + r) * nfun * P;
       for (int mm = lane; mm < nfun; mm += 64) {
         const float eta = prow[mm * P], rc = prow[mm * P + P - 1];
@@ -323,12 +318,7 @@ __global__ __launch_bounds__(64) void acsf_endpoint_sum_kernel(AcsfArgs a, int K
       s0 += src[0]; s1 += src[1]; s2 += src[2];
     }
   }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    s0 += __shfl_xor(s0, off);
-    s1 += __shfl_xor(s1, off);
-    s2 += __shfl_xor(s2, off);
-  }
+  s0 = mp_wave_sum(s0); s1 = mp_wave_sum(s1); s2 = mp_wave_sum(s2);
   if (lane == 0) {
     dx[3 * n] = s0; dx[3 * n + 1] = s1; dx[3 * n + 2] = s2;
   }

@@ -58,12 +58,6 @@ __global__ void euclidean_norm_grad_kernel(const float* __restrict__ x, const fl
   }
 }
 
-__device__ __forceinline__ float ipow(float x, int n) {
-  float r = 1.0f;
-  for (int i = 0; i < n; ++i) r *= x;
-  return r;
-}
-
 // d/dd of BesselBasisLayer (geom.py:772-785): sum_k gy[e,k] * (env'(x) sin(f x) + env(x) f cos(f x)) / cutoff
 __global__ void bessel_grad_kernel(const float* __restrict__ d, int64_t M, const float* __restrict__ freq,
                                    int num_radial, float inv_cutoff, int p, float a, float b, float c,
@@ -73,7 +67,7 @@ __global__ void bessel_grad_kernel(const float* __restrict__ d, int64_t M, const
     const float xs = d[e] * inv_cutoff;
     float acc = 0.0f;
     if (xs < 1.0f && xs > 0.0f) {
-      const float xp2 = ipow(xs, p - 2);
+      const float xp2 = mp_ipow(xs, p - 2);
       const float xp1 = xp2 * xs;
       const float env = 1.0f / xs + a * xp1 + b * (xp1 * xs) + c * (xp1 * xs * xs);
       const float denv = -1.0f / (xs * xs) + a * (p - 1) * xp2 + b * p * xp1 + c * (p + 1) * (xp1 * xs);

@@ -90,12 +90,6 @@ __device__ __forceinline__ double pair_df(double r, double gamma) {
   return (kTwoOverSqrtPi * a * exp(-(a * r) * (a * r)) * r - erf(a * r)) / (r * r);
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
 template <bool REVERSE>
 __device__ void cent_write_nan(const CentArgs& a, int64_t base, int n) {
   const float qnan = __int_as_float(0x7fc00000);
@@ -199,8 +193,8 @@ __global__ __launch_bounds__(64) void cent_solve_kernel(CentArgs a) {
 
   double su = 0.0, sv = 0.0;
   for (int i = lane; i < n; i += 64) { su += s_u[i]; sv += s_v[i]; }
-  su = wave_sum(su);
-  sv = wave_sum(sv);
+  su = mp_wave_sum(su);
+  sv = mp_wave_sum(sv);
   if (!REVERSE) {
     const double lam = (sv - static_cast<double>(a.qtot[g])) / su;
     for (int i = lane; i < n; i += 64) a.q_out[base + i] = static_cast<float>(s_v[i] - lam * s_u[i]);
@@ -261,8 +255,8 @@ __global__ __launch_bounds__(64) void gauss_energy_kernel(GaussArgs a) {
     const double si = atom_sigma(a, i), qi = a.q[i];
     if (si != 0.0) self += qi * qi / si;
   }
-  pair = wave_sum(pair);
-  self = wave_sum(self);
+  pair = mp_wave_sum(pair);
+  self = mp_wave_sum(self);
   if (lane == 0) {
     if (a.mult != 0.0f) pair /= static_cast<double>(a.mult);
     a.energy[g] = static_cast<float>(pair + self / (2.0 * kSqrtPi));

@@ -191,12 +191,12 @@ __global__ __launch_bounds__(512, 1) void dense_chain_kernel(ChainArgs a) {
 //   chain  a = act(c Wd + bd) Wa + ba            (the <256, 1, 3> chain above)
 //   post   z2 = z + (prod a_sv + a_ss) ,  v2[k] = v[k] + a_vv v_u[k]      with a = [a_vv | a_sv | a_ss]   (+ PAiNN.py:131-132)
 //
-// with uv (3N, 2F) = v [Wu | Wv] from the chain launch before it.  The two element-wise kernels this replaces
-// (csrc/mp_painn_fused.hip: painn_update_pre / painn_update_post, ~5 us each at 64 graphs - launch floor - six per
-// forward) become the prologue and the epilogue of the chain: thread t of the 512 owns node t / 32 of the tile and the
+// with uv (3N, 2F) = v [Wu | Wv] from the chain launch before it.  The two element-wise kernels this replaced
+// (a pre and a post step around the chain, since removed: ~5 us each at 64 graphs - launch floor - six per
+// forward) became the prologue and the epilogue of the chain: thread t of the 512 owns node t / 32 of the tile and the
 // four features 4 (t % 32) ..; what the epilogue needs again (z, prod, v_u, v) waits in LDS, the 16 x 384 output tile
 // is exchanged through LDS (a node's a_vv / a_sv / a_ss columns belong to different waves).  Same arithmetic, same
-// order as the separate kernels.  c / prod / a reach HBM only when the caller asks (the reverse pass reads them).
+// order as the separate kernels had.  c / prod / a reach HBM only when the caller asks (the reverse pass reads them).
 struct UpdateArgs {
   int64_t N;
   int ntiles;
@@ -264,7 +264,7 @@ __global__ __launch_bounds__(512, 1) void painn_update_chain_kernel(UpdateArgs a
   for (int tile = blockIdx.x; tile < a.ntiles; tile += nblocks) {
     const int64_t row0 = static_cast<int64_t>(tile) * 16;
     const int64_t erow = row0 + er;
-    // ---- pre (painn_update_pre_kernel's arithmetic, k order) ----
+    // ---- pre (k order) ----
     const float4 vu[3] = {vu0, vu1, vu2}, vv[3] = {vv0, vv1, vv2}, vq[3] = {vq0, vq1, vq2};
     float pr[4] = {0.f, 0.f, 0.f, 0.f}, sq[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -328,7 +328,7 @@ __global__ __launch_bounds__(512, 1) void painn_update_chain_kernel(UpdateArgs a
         if (a.a_out && row < a.N) a.a_out[row * UPD_UO + col] = v;
       }
     __syncthreads();
-    // ---- post (painn_update_post_kernel's arithmetic) ----
+    // ---- post ----
     if (erow < a.N) {
       const float4 a_vv = *reinterpret_cast<const float4*>(At + er * UPD_AT_LD + ef);
       const float4 a_sv = *reinterpret_cast<const float4*>(At + er * UPD_AT_LD + UPD_F + ef);
@@ -352,12 +352,12 @@ __global__ __launch_bounds__(512, 1) void painn_update_chain_kernel(UpdateArgs a
   }
 }
 
-// Reverse of the fused PAiNNUpdate above, one launch per block (replaces painn_update_post_bwd / painn_update_pre_bwd of
-// csrc/mp_painn_fused.hip around the <384, 1, 2> reverse chain):
+// Reverse of the fused PAiNNUpdate above, one launch per block (it replaced two element-wise kernels, since removed,
+// around the <384, 1, 2> reverse chain):
 //   prologue  g_a = [sum_k g_v2[k] v_u[k] | g_z2 prod | g_z2] ,  g_prod = g_z2 a_sv
 //   chain     g_c = ((g_a Wa^T) * act'(h2)) Wd^T                                   (N, 2F)
 //   epilogue  g_z = g_z2 + g_c[:, :F] ,  g_vu[k] = g_v2[k] a_vv + g_prod v_v[k] ,  g_vv[k] = g_prod v_u[k] + g_c[:, F:] v_v[k] / ||v_v||
-// Same arithmetic, same order as the separate kernels; everything the epilogue needs again waits in LDS (13 x 8 KB).
+// Same arithmetic, same order as the separate kernels had; everything the epilogue needs again waits in LDS (13 x 8 KB).
 struct UpdateBwdArgs {
   int64_t N;
   int ntiles;
@@ -427,7 +427,7 @@ __global__ __launch_bounds__(512, 1) void painn_update_bwd_chain_kernel(UpdateBw
   for (int tile = blockIdx.x; tile < a.ntiles; tile += nblocks) {
     const int64_t row0 = static_cast<int64_t>(tile) * 16;
     const int64_t erow = row0 + er;
-    // ---- prologue (painn_update_post_bwd_kernel's arithmetic) ----
+    // ---- prologue ----
     const float4 gavv = make_float4((0.0f + gv0.x * vu0.x + gv1.x * vu1.x) + gv2.x * vu2.x,
                                     (0.0f + gv0.y * vu0.y + gv1.y * vu1.y) + gv2.y * vu2.y,
                                     (0.0f + gv0.z * vu0.z + gv1.z * vu1.z) + gv2.z * vu2.z,
@@ -477,7 +477,7 @@ __global__ __launch_bounds__(512, 1) void painn_update_bwd_chain_kernel(UpdateBw
         Gt[lrow * UB_GT_LD + col] = acc2[cb][r];
       }
     __syncthreads();
-    // ---- epilogue (painn_update_pre_bwd_kernel's arithmetic) ----
+    // ---- epilogue ----
     if (erow < a.N) {
       const float4 gc0 = *reinterpret_cast<const float4*>(Gt + er * UB_GT_LD + ef);
       const float4 gc1 = *reinterpret_cast<const float4*>(Gt + er * UB_GT_LD + UPD_F + ef);

@@ -1,4 +1,4 @@
-// Shared host-side helpers of libmpengine (gfx950 only).
+// Shared host-side and device-side helpers of libmpengine (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -24,6 +24,10 @@ inline int check_launch(const char* what) {
 }
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// workspace carving: sub-buffers start on 256-B boundaries; the 16-B vector paths ask for aligned16 operands
+inline size_t align256(size_t n) { return (n + 255) & ~static_cast<size_t>(255); }
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // Grid for a grid-stride elementwise kernel: enough blocks to fill 256 CUs x 8, never more than the work.
 inline unsigned grid_for(int64_t work_items, int block = 256) {
@@ -77,6 +81,37 @@ __device__ __forceinline__ void mp_publish_flags(int32_t* flags, int local_flags
   if (wave_flags != 0 && (threadIdx.x & 63) == 0) {
     if ((__atomic_load_n(flags, __ATOMIC_RELAXED) & wave_flags) != wave_flags) atomicOr(flags, wave_flags);
   }
+}
+
+// largest g in [0, G) with splits[g] <= e  (graph owning flat element e); splits has G+1 entries.
+__device__ __forceinline__ int64_t mp_owner_of(const int64_t* __restrict__ splits, int64_t G, int64_t e) {
+  int64_t lo = 0, hi = G;  // invariant: splits[lo] <= e < splits[hi]
+  while (hi - lo > 1) {
+    int64_t mid = (lo + hi) >> 1;
+    if (splits[mid] <= e) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// x^n by repeated multiplication, n >= 0 (the polynomial envelopes: n is a small layer constant)
+__device__ __forceinline__ float mp_ipow(float x, int n) {
+  float r = 1.0f;
+  for (int i = 0; i < n; ++i) r *= x;
+  return r;
+}
+
+// value of lane `lane` (wave-uniform index) in every lane: v_readlane_b32, the result lives in a scalar register
+__device__ __forceinline__ float mp_bcast(float v, int lane) {
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
+}
+__device__ __forceinline__ int mp_bcast(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
+
+// Sum over the 64 lanes of the wave, left in every lane: xor butterfly from 32 down to 1 (fixed order: deterministic).
+template <typename T>
+__device__ __forceinline__ T mp_wave_sum(T v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
 }
 
 __device__ __forceinline__ float mp_softplus(float x) {

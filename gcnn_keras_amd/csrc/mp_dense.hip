@@ -240,7 +240,7 @@ __global__ void softmax_rows_kernel(const float* __restrict__ x, int64_t R, int6
     for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
     float sum = 0.0f;
     for (int64_t c = lane; c < C; c += 64) sum += expf(row[c] - mx);
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    sum = mp_wave_sum(sum);
     for (int64_t c = lane; c < C; c += 64) out[r * C + c] = expf(row[c] - mx) / sum;
   }
 }
@@ -260,14 +260,14 @@ __global__ void layer_norm_rows_kernel(const float* __restrict__ x, int64_t R, i
     const float* row = x + r * C;
     float sum = 0.0f;
     for (int64_t c = lane; c < C; c += 64) sum += row[c];
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    sum = mp_wave_sum(sum);
     const float mean = sum * inv_c;
     float sq = 0.0f;
     for (int64_t c = lane; c < C; c += 64) {
       const float d = row[c] - mean;
       sq += d * d;
     }
-    for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o, 64);
+    sq = mp_wave_sum(sq);
     const float rstd = rsqrtf(sq * inv_c + eps);
     for (int64_t c = lane; c < C; c += 64) {
       const float inv = gamma ? rstd * gamma[c] : rstd;

@@ -21,16 +21,8 @@ constexpr int kIntEmb = 64;     // int_emb_size of the fused triplet step
 constexpr int kBasisEmb = 8;    // basis_emb_size of the fused triplet step
 constexpr int kMaxSbf = 64;     // num_spherical * num_radial of the fused triplet step
 
-__device__ __forceinline__ float bcast(float v, int s) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), s));
-}
-__device__ __forceinline__ int bcast(int v, int s) { return __builtin_amdgcn_readlane(v, s); }
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-  return bcast(v, 0);
-}
+// wave-wide sum as a wave-uniform (scalar-register) value
+__device__ __forceinline__ float wave_sum(float v) { return mp_bcast(mp_wave_sum(v), 0); }
 
 // ------------------------------------------------------------------------------------------------ angles
 // VectorAngle: theta = atan2(|a x b|, a . b)
@@ -355,11 +347,11 @@ __global__ __launch_bounds__(64) void triplet_fwd_kernel(const float* __restrict
     const float h = triplet_h(sbf, nsbf, s_w1, t, ok, k);
     const int cnt = min(8, end - base);
     for (int s = 0; s < cnt; ++s) {
-      const int ms = bcast(m, 8 * s);
+      const int ms = mp_bcast(m, 8 * s);
       if (ms < 0) continue;
       float v = 0.0f;
 #pragma unroll
-      for (int q = 0; q < kBasisEmb; ++q) v += bcast(h, 8 * s + q) * w2[q];
+      for (int q = 0; q < kBasisEmb; ++q) v += mp_bcast(h, 8 * s + q) * w2[q];
       acc += xdown[static_cast<int64_t>(ms) * kIntEmb + lane] * v;
     }
   }
@@ -399,12 +391,12 @@ __global__ __launch_bounds__(64) void triplet_bwd_kernel(const float* __restrict
     const float h = triplet_h(sbf, nsbf, s_w1, t, n >= 0, k);
     const int cnt = min(8, end - base);
     for (int s = 0; s < cnt; ++s) {
-      const int ns = bcast(n, 8 * s);
-      const int64_t ts = static_cast<int64_t>(static_cast<uint32_t>(bcast(ti, 8 * s)));
+      const int ns = mp_bcast(n, 8 * s);
+      const int64_t ts = static_cast<int64_t>(static_cast<uint32_t>(mp_bcast(ti, 8 * s)));
       const float gc = ns >= 0 ? g[static_cast<int64_t>(ns) * kIntEmb + lane] : 0.0f;
       float v = 0.0f;
 #pragma unroll
-      for (int q = 0; q < kBasisEmb; ++q) v += bcast(h, 8 * s + q) * w2[q];
+      for (int q = 0; q < kBasisEmb; ++q) v += mp_bcast(h, 8 * s + q) * w2[q];
       acc += gc * v;
       if (sbf_bar) {
         const float uc = gc * xd;

@@ -6,16 +6,6 @@
 
 namespace mp_prep {
 
-// largest g in [0, G) with splits[g] <= e
-__device__ __forceinline__ int64_t owner_of(const int64_t* __restrict__ splits, int64_t G, int64_t e) {
-  int64_t lo = 0, hi = G;
-  while (hi - lo > 1) {
-    int64_t mid = (lo + hi) >> 1;
-    if (splits[mid] <= e) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
 // owner search on a staged (LDS) copy of the splits
 __device__ __forceinline__ int owner_of_lds(const int64_t* splits, int G, int64_t e) {
   int lo = 0, hi = G;
@@ -98,7 +88,7 @@ __device__ __forceinline__ void edge_prepare_body(const EdgePrepArgs& p, int64_t
       g_start = s_es[g];
     } else {
       const int64_t e_wave = __builtin_amdgcn_readfirstlane(static_cast<int>(e - (threadIdx.x & 63)));
-      g = owner_of(edge_splits, G, e_wave < M ? e_wave : M - 1);
+      g = mp_owner_of(edge_splits, G, e_wave < M ? e_wave : M - 1);
       if (e >= M) continue;
       while (g + 1 < G && edge_splits[g + 1] <= e) ++g;
       base = node_splits[g];

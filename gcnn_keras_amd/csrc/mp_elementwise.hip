@@ -79,12 +79,6 @@ __global__ void gauss_basis_kernel(const float* __restrict__ d, int64_t M, int b
   }
 }
 
-__device__ __forceinline__ float ipow(float x, int n) {
-  float r = 1.0f;
-  for (int i = 0; i < n; ++i) r *= x;
-  return r;
-}
-
 // kgcnn/layers/geom.py:772-785: d_scaled = d * (1/cutoff); env = 1/x + a x^(p-1) + b x^p + c x^(p+1), 0 for x >= 1
 __global__ void bessel_basis_kernel(const float* __restrict__ d, int64_t M, const float* __restrict__ freq,
                                     int num_radial, float inv_cutoff, int p, float a, float b, float c,
@@ -95,7 +89,7 @@ __global__ void bessel_basis_kernel(const float* __restrict__ d, int64_t M, cons
     const int k = static_cast<int>(t % num_radial);
     const int64_t e = t / num_radial;
     const float xs = d[e] * inv_cutoff;
-    const float xp1 = ipow(xs, p - 1);
+    const float xp1 = mp_ipow(xs, p - 1);
     const float env = 1.0f / xs + a * xp1 + b * (xp1 * xs) + c * (xp1 * xs * xs);
     const float cut = xs < 1.0f ? env : 0.0f;
     out[t] = cut * sinf(freq[k] * xs);
@@ -133,15 +127,6 @@ __global__ void edge_geometry_kernel(const float* __restrict__ xyz, int64_t N, c
       dir[e * 3 + 2] = dz * inv;
     }
   }
-}
-
-__device__ __forceinline__ int64_t owner_of(const int64_t* __restrict__ splits, int64_t G, int64_t e) {
-  int64_t lo = 0, hi = G;
-  while (hi - lo > 1) {
-    int64_t mid = (lo + hi) >> 1;
-    if (splits[mid] <= e) lo = mid; else hi = mid;
-  }
-  return lo;
 }
 
 __global__ void ragged_to_padded_kernel(const float* __restrict__ values, const int64_t* __restrict__ splits,

@@ -49,15 +49,6 @@ __global__ void gather_cols_kernel(const VecT* __restrict__ x, int64_t N, int64_
   }
 }
 
-__device__ __forceinline__ int64_t owner_of(const int64_t* __restrict__ splits, int64_t G, int64_t e) {
-  int64_t lo = 0, hi = G;
-  while (hi - lo > 1) {
-    int64_t mid = (lo + hi) >> 1;
-    if (splits[mid] <= e) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
 template <typename VecT>
 __global__ void gather_i64_kernel(const VecT* __restrict__ x, int64_t N, int64_t chunks,
                                   const int64_t* __restrict__ idx, int64_t M, int K, int col,
@@ -72,7 +63,7 @@ __global__ void gather_i64_kernel(const VecT* __restrict__ x, int64_t N, int64_t
     const int k = static_cast<int>(ec % ncols);
     const int64_t e = ec / ncols;
     int64_t row = idx[e * K + (col < 0 ? k : col)];
-    if (node_splits) row += node_splits[owner_of(edge_splits, G, e)];
+    if (node_splits) row += node_splits[mp_owner_of(edge_splits, G, e)];
     VecT v{};
     if (row >= 0 && row < N) v = x[row * chunks + c];  // TF-GPU semantics: out-of-range rows read as zeros
     out[t] = v;
@@ -87,7 +78,7 @@ __global__ void repeat_rows_kernel(const VecT* __restrict__ state, const int64_t
   for (int64_t t = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; t < total; t += stride) {
     const int64_t c = t % chunks;
     const int64_t n = t / chunks;
-    out[t] = state[owner_of(splits, G, n) * chunks + c];
+    out[t] = state[mp_owner_of(splits, G, n) * chunks + c];
   }
 }
 
@@ -108,7 +99,6 @@ __global__ void embedding_kernel(const VecT* __restrict__ table, int64_t vocab, 
   }
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 
@@ -126,7 +116,7 @@ int mp_gather_rows_f32(const float* x, int64_t N, int64_t row_elems, const int32
     sel[i] = colsel_host[i];
   }
   hipStream_t s = mp::as_stream(stream);
-  if (row_elems % 4 == 0 && aligned16(x) && aligned16(out)) {
+  if (row_elems % 4 == 0 && mp::aligned16(x) && mp::aligned16(out)) {
     const int64_t chunks = row_elems / 4;
     gather_cols_kernel<float4><<<mp::grid_for(M * ncols * chunks), 256, 0, s>>>(
         reinterpret_cast<const float4*>(x), N, chunks, cols, M, ncols, sel[0], sel[1], sel[2], sel[3],
@@ -149,7 +139,7 @@ int mp_gather_rows_i64_f32(const float* x, int64_t N, int64_t row_elems, const i
   MP_REQUIRE(node_splits == nullptr || G > 0, "mp_gather_rows_i64_f32: no graphs");
   const int ncols = col < 0 ? K : 1;
   hipStream_t s = mp::as_stream(stream);
-  if (row_elems % 4 == 0 && aligned16(x) && aligned16(out)) {
+  if (row_elems % 4 == 0 && mp::aligned16(x) && mp::aligned16(out)) {
     const int64_t chunks = row_elems / 4;
     gather_i64_kernel<float4><<<mp::grid_for(M * ncols * chunks), 256, 0, s>>>(
         reinterpret_cast<const float4*>(x), N, chunks, idx, M, K, col, node_splits, edge_splits, G,
@@ -167,7 +157,7 @@ int mp_repeat_rows_f32(const float* state, const int64_t* splits, int64_t G, int
   if (N == 0) return MP_OK;
   MP_REQUIRE(state && splits && out && G > 0, "mp_repeat_rows_f32: null pointer / no graphs");
   hipStream_t s = mp::as_stream(stream);
-  if (row_elems % 4 == 0 && aligned16(state) && aligned16(out)) {
+  if (row_elems % 4 == 0 && mp::aligned16(state) && mp::aligned16(out)) {
     const int64_t chunks = row_elems / 4;
     repeat_rows_kernel<float4><<<mp::grid_for(N * chunks), 256, 0, s>>>(reinterpret_cast<const float4*>(state), splits,
                                                                        G, chunks, N, reinterpret_cast<float4*>(out));
@@ -183,7 +173,7 @@ int mp_embedding_f32(const float* table, int64_t vocab, int64_t dim, const float
   if (N == 0) return MP_OK;
   MP_REQUIRE(table && numbers && out, "mp_embedding_f32: null pointer");
   hipStream_t s = mp::as_stream(stream);
-  if (dim % 4 == 0 && aligned16(table) && aligned16(out)) {
+  if (dim % 4 == 0 && mp::aligned16(table) && mp::aligned16(out)) {
     const int64_t chunks = dim / 4;
     embedding_kernel<float4><<<mp::grid_for(N * chunks), 256, 0, s>>>(reinterpret_cast<const float4*>(table), vocab,
                                                                      chunks, numbers, N,

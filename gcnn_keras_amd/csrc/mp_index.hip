@@ -13,22 +13,12 @@
 
 namespace {
 
-// largest g in [0, G) with splits[g] <= e  (graph owning flat element e); splits has G+1 entries.
-__device__ __forceinline__ int64_t owner_of(const int64_t* __restrict__ splits, int64_t G, int64_t e) {
-  int64_t lo = 0, hi = G;  // invariant: splits[lo] <= e < splits[hi]
-  while (hi - lo > 1) {
-    int64_t mid = (lo + hi) >> 1;
-    if (splits[mid] <= e) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
 __global__ void shift_index_kernel(const int64_t* __restrict__ idx, int64_t M, int K,
                                    const int64_t* __restrict__ node_splits, const int64_t* __restrict__ edge_splits,
                                    int64_t G, int64_t sign, int64_t* __restrict__ out) {
   const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
   for (int64_t e = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; e < M; e += stride) {
-    const int64_t shift = sign * node_splits[owner_of(edge_splits, G, e)];
+    const int64_t shift = sign * node_splits[mp_owner_of(edge_splits, G, e)];
     if (K == 2) {
       // one 16-byte row per lane: dwordx4 load / store
       const longlong2 v = reinterpret_cast<const longlong2*>(idx)[e];
@@ -49,14 +39,14 @@ __global__ void index_prepare_kernel(const int64_t* __restrict__ idx, int64_t M,
        e += stride) {
     // one wave-uniform owner search (scalar loads) for the wave's first edge, then a short per-lane walk
     const int64_t e_wave = __builtin_amdgcn_readfirstlane(static_cast<int>(e - (threadIdx.x & 63)));
-    int64_t g = owner_of(edge_splits, G, e_wave < M ? e_wave : M - 1);
+    int64_t g = mp_owner_of(edge_splits, G, e_wave < M ? e_wave : M - 1);
     if (e >= M) continue;
     while (g + 1 < G && edge_splits[g + 1] <= e) ++g;
     const int64_t base = node_splits[g];
     const int64_t n_g = node_splits[g + 1] - base;
     // shift of the previous edge (for the sortedness check of the batch-level ids)
     int64_t base_prev = base;
-    if (e > 0 && edge_splits[g] > e - 1) base_prev = node_splits[owner_of(edge_splits, G, e - 1)];
+    if (e > 0 && edge_splits[g] > e - 1) base_prev = node_splits[mp_owner_of(edge_splits, G, e - 1)];
     for (int k = 0; k < K; ++k) {
       int64_t v = idx[e * K + k];
       if (v < 0 || v >= n_g) {
@@ -103,7 +93,6 @@ __global__ void iota_kernel(int32_t* __restrict__ out, int64_t n) {
     out[i] = static_cast<int32_t>(i);
 }
 
-inline size_t align256(size_t x) { return (x + 255) & ~static_cast<size_t>(255); }
 
 }  // namespace
 
@@ -181,7 +170,7 @@ int mp_sort_workspace_bytes(int64_t M, size_t* bytes_out_host) {
     mp::set_error("rocprim temp-size query failed: %s", hipGetErrorString(e));
     return MP_EHIP;
   }
-  *bytes_out_host = align256(temp) + align256(sizeof(int32_t) * static_cast<size_t>(M > 0 ? M : 1));
+  *bytes_out_host = mp::align256(temp) + mp::align256(sizeof(int32_t) * static_cast<size_t>(M > 0 ? M : 1));
   return MP_OK;
 }
 
@@ -196,8 +185,8 @@ int mp_sort_segments_i32(const int32_t* seg, int64_t M, int32_t* seg_sorted, int
   MP_REQUIRE(ws_bytes >= need, "mp_sort_segments_i32: workspace %zu < %zu bytes", ws_bytes, need);
   hipStream_t s = mp::as_stream(stream);
   int32_t* iota = static_cast<int32_t*>(ws);
-  void* temp = static_cast<char*>(ws) + align256(sizeof(int32_t) * static_cast<size_t>(M));
-  size_t temp_bytes = ws_bytes - align256(sizeof(int32_t) * static_cast<size_t>(M));
+  void* temp = static_cast<char*>(ws) + mp::align256(sizeof(int32_t) * static_cast<size_t>(M));
+  size_t temp_bytes = ws_bytes - mp::align256(sizeof(int32_t) * static_cast<size_t>(M));
   iota_kernel<<<mp::grid_for(M), 256, 0, s>>>(iota, M);
   // LSD radix sort is stable: equal receivers keep their original edge order, as tf.argsort(stable=True) does.
   MP_HIP(rocprim::radix_sort_pairs(temp, temp_bytes, seg, seg_sorted, iota, perm, static_cast<size_t>(M), 0, 32, s,

@@ -4,22 +4,22 @@
 //
 //   GEMM  h1 = z W1 + b1                       GEMM  s = swish(h1) Wphi + bphi          (mp_dense_ex_f32, prologue swish)
 //   EDGE  z' = z + sum_e s_j w_e |1 ,  v' = v + sum_e (s_j w_e)|2 (x) v_j + (s_j w_e)|3 (x) r_ij      (painn_message_kernel)
-//   GEMM  [v_u | v_v] = v' [Wu | Wv]            NODE  c = [z' | ||v_v||],  prod = <v_u, v_v>          (painn_update_pre)
+//   GEMM  [v_u | v_v] = v' [Wu | Wv]            NODE  c = [z' | ||v_v||],  prod = <v_u, v_v>
 //   GEMM  h2 = c Wd + bd                        GEMM  a = swish(h2) Wa + ba
-//   NODE  z'' = z' + prod a_sv + a_ss ,  v'' = v' + a_vv (x) v_u                                       (painn_update_post)
+//   NODE  z'' = z' + prod a_sv + a_ss ,  v'' = v' + a_vv (x) v_u
 //
-// i.e. five GEMMs on the FP32 matrix cores and three memory-bound kernels per block instead of the ~30 primitive launches
-// of the layer path; none of the (M,3F) / (M,3,F) edge tensors of the reference exists.  The reverse pass mirrors it
-// kernel for kernel (transposed-weight GEMMs with the activation derivative fused as a prologue; the edge kernel runs
+// (everything after the [v_u | v_v] GEMM is ONE launch, mp_painn_update_fused_f32 in csrc/mp_chain.hip) instead of the ~30
+// primitive launches of the layer path; none of the (M,3F) / (M,3,F) edge tensors of the reference exists.  The reverse
+// pass mirrors it kernel for kernel (transposed-weight GEMMs with the activation derivative fused as a prologue; the edge kernel runs
 // SENDER-parallel over the CSR of column 1, because the message's inputs s_j, v_j live at the sender: their gradients
 // are then register accumulations of one wave, no atomics, fixed order).  Distances enter through the radial basis and
 // the unit vectors only, so the edge kernel reduces dE/d(rbf_e) to ONE scalar per edge with the basis derivative
 // rbf'(d_e) prepared by stage 0:  dE/dd_e = sum_f g_w[f] (rbf'_e Ww)[f];  a last node-parallel kernel turns
 // (dE/dd_e, dE/dr_ij) into dE/dx over both CSRs.
 //
-// All kernels are HBM/L2-bound streaming or gather kernels except the GEMMs; the per-edge filter (K = B = 20) is far too
-// thin for MFMA tiles and runs on the VALU as packed FP32 FMAs with the lane's weight columns in registers.
-#include <cstdlib>
+// All kernels are HBM/L2-bound streaming or gather kernels except the GEMMs.  The per-edge filter (K = B = 20) runs on the
+// VALU as packed FP32 FMAs with the lane's weight columns in registers in the gather kernels, and on the matrix pipe
+// (bf16x3) in the LDS tile kernels.
 #include <mutex>
 
 #include "mp_common.h"
@@ -41,27 +41,10 @@ __device__ __forceinline__ void pk_fma_whi(floatx2& acc, floatx2 x, floatx2 wpai
   asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "+v"(acc) : "s"(x), "v"(wpair));
 }
 
-__device__ __forceinline__ float ipow(float x, int n) {
-  float r = 1.0f;
-  for (int i = 0; i < n; ++i) r *= x;
-  return r;
-}
-
-// v_readlane_b32 of a float register (lane index wave-uniform)
-__device__ __forceinline__ float readlane_f(float v, int l) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-// Wave-wide sum on the VALU's DPP path, result wave-uniform: two quad permutes, row_half_mirror, row_mirror (after which
-// every lane of a 16-lane row holds the row's sum) and four v_readlane for the rows.  The xor-shuffle form above goes
-// through the LDS crossbar (ds_bpermute): six dependent round trips per value - the message reverse kernel reduces four
-// values per edge, 96 ds_bpermute per 4-edge chunk before, none now.  Fixed order: deterministic.
+// Wave-wide sums on the VALU's DPP path: two quad permutes, row_half_mirror, row_mirror (after which every lane of a
+// 16-lane row holds the row's sum) and v_readlane for the rows.  The xor-shuffle form (mp_wave_sum) goes through the LDS
+// crossbar (ds_bpermute): six dependent round trips per value - the message reverse kernel reduces four values per edge,
+// 96 ds_bpermute per 4-edge chunk that way, none with wave_sum4_uniform below.  Fixed order: deterministic.
 template <int CTRL>
 __device__ __forceinline__ float dpp_mov(float v) {
   return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
@@ -147,13 +130,6 @@ __device__ __forceinline__ float sum_halves(float x) {
   const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
   return __uint_as_float(r[0]) + __uint_as_float(r[1]);
 }
-__device__ __forceinline__ float wave_sum_uniform(float v) {
-  v += dpp_mov<0xB1>(v);    // quad_perm [1,0,3,2]
-  v += dpp_mov<0x4E>(v);    // quad_perm [2,3,0,1]
-  v += dpp_mov<0x141>(v);   // row_half_mirror
-  v += dpp_mov<0x140>(v);   // row_mirror
-  return (readlane_f(v, 0) + readlane_f(v, 16)) + (readlane_f(v, 32) + readlane_f(v, 48));
-}
 
 // Four wave-wide sums at once (results wave-uniform): gfx950's v_permlane32_swap / v_permlane16_swap fold two registers
 // per instruction - (a, b) and (c, d) over the wave halves, then the two results over the row pairs - leaving row 0 with
@@ -171,10 +147,10 @@ __device__ __forceinline__ void wave_sum4_uniform(float& a, float& b, float& c, 
   v += dpp_mov<0x4E>(v);    // quad_perm [2,3,0,1]
   v += dpp_mov<0x141>(v);   // row_half_mirror
   v += dpp_mov<0x140>(v);   // row_mirror
-  a = readlane_f(v, 0);
-  c = readlane_f(v, 16);
-  b = readlane_f(v, 32);
-  d = readlane_f(v, 48);
+  a = mp_bcast(v, 0);
+  c = mp_bcast(v, 16);
+  b = mp_bcast(v, 32);
+  d = mp_bcast(v, 48);
 }
 
 // ---------------------------------------------------------------------------------------------------- stage 0
@@ -217,7 +193,7 @@ __global__ __launch_bounds__(256) void painn_basis_kernel(PainnBasisArgs q) {
     const int k = static_cast<int>(t % q.B);
     const float s = q.dist[e];
     const float xs = s * q.inv_cutoff;
-    const float xp1 = ipow(xs, q.p - 1);
+    const float xp1 = mp_ipow(xs, q.p - 1);
     const float envp = 1.0f / xs + q.a * xp1 + q.b * (xp1 * xs) + q.c * (xp1 * xs * xs);
     const float cut = xs < 1.0f ? envp : 0.0f;
     const float f = q.freq[k];
@@ -226,7 +202,7 @@ __global__ __launch_bounds__(256) void painn_basis_kernel(PainnBasisArgs q) {
     if (q.rbfd != nullptr) {
       float dv = 0.0f;
       if (xs < 1.0f && xs > 0.0f) {
-        const float xp2 = ipow(xs, q.p - 2);
+        const float xp2 = mp_ipow(xs, q.p - 2);
         const float xq1 = xp2 * xs;
         const float env_in = 1.0f / xs + q.a * xq1 + q.b * (xq1 * xs) + q.c * (xq1 * xs * xs);
         const float denv = -1.0f / (xs * xs) + q.a * (q.p - 1) * xp2 + q.b * q.p * xq1 + q.c * (q.p + 1) * (xq1 * xs);
@@ -371,8 +347,8 @@ __global__ __launch_bounds__(256) void painn_message_kernel(PainnMsgArgs a) {
 #pragma unroll
             for (int q = 0; q < MAXB / 2; ++q) {
               if (2 * q < B) {
-                const floatx2 x0 = {readlane_f(meta[u], 2 * q), readlane_f(meta[u + 1], 2 * q)};
-                const floatx2 x1 = {readlane_f(meta[u], 2 * q + 1), readlane_f(meta[u + 1], 2 * q + 1)};
+                const floatx2 x0 = {mp_bcast(meta[u], 2 * q), mp_bcast(meta[u + 1], 2 * q)};
+                const floatx2 x1 = {mp_bcast(meta[u], 2 * q + 1), mp_bcast(meta[u + 1], 2 * q + 1)};
 #pragma unroll
                 for (int p = 0; p < 3; ++p) {
                   pk_fma_wlo(ff[p], x0, wp[p][q]);
@@ -383,7 +359,7 @@ __global__ __launch_bounds__(256) void painn_message_kernel(PainnMsgArgs a) {
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
               if (u0 + u + h < cnt) {   // wave-uniform
-                const float envv = a.env ? readlane_f(meta[u + h], B + 3) : 1.0f;
+                const float envv = a.env ? mp_bcast(meta[u + h], B + 3) : 1.0f;
                 float sw[3];
 #pragma unroll
                 for (int p = 0; p < 3; ++p) {
@@ -394,7 +370,7 @@ __global__ __launch_bounds__(256) void painn_message_kernel(PainnMsgArgs a) {
                 ds += sw[0];
 #pragma unroll
                 for (int k = 0; k < 3; ++k) {
-                  const float rk = readlane_f(meta[u + h], B + k);
+                  const float rk = mp_bcast(meta[u + h], B + k);
                   dv[k] += sw[1] * vj[u + h][k] + sw[2] * rk;   // (sw2 * v_j) + (sw3 * r_ij)
                 }
               }
@@ -414,24 +390,12 @@ __global__ __launch_bounds__(256) void painn_message_kernel(PainnMsgArgs a) {
   }
 }
 
-// ---------------------------------------------------------------------------------------------------- message, MFMA
-// The same message step with the per-edge filter  w_e = rbf_e Ww + bw  (K = B + 1 <= 32 -> 3F = 384 columns, 15 kflop per
-// edge: 85 % of the step's arithmetic) on the matrix pipe instead of 60 FMAs per lane and edge on the VALU.  FP32-exact
-// as in csrc/mp_cfconv.hip: both operands are split into three bf16 pieces (8 + 8 + 8 mantissa bits, every difference exact
-// in FP32) and the six leading cross products run on v_mfma_f32_32x32x16_bf16 with FP32 accumulation (the dropped products
-// are below 2^-24 of |a||b|, the rounding of one FP32 product).
-//
-// Work split: a workgroup of four waves serves a PAIR of receiving nodes, wave q the feature quarter 32 q .. 32 q + 31 of
-// all three filter parts.  One MFMA tile = 32 edge rows x 32 features: the accumulator leaves rows {0-3, 8-11, 16-19,
-// 24-27} in lanes 0-31 and rows {4-7, 12-15, ...} in lanes 32-63, sixteen rows per lane - so lane half h is given the
-// edges of receiver 2 pair + h (row m of the A operand = edge (m & 3) + 4 (m >> 3) of the half (m >> 2) & 1), and each half
-// walks ITS receiver's edges in register order = edge order (the order of tf.math.segment_sum after the stable sort:
-// deterministic, no atomics, no cross-lane step at all).  A lane = one feature of one receiver: the sender rows s_j, v_j
-// arrive as 128-B pieces (32 lanes x 4 B), eight edges in flight per lane.  Rows beyond a receiver's edge count carry a
-// zero A row (bias slot included), so their filter - and message - is exactly 0; their loads re-read a valid edge.
-// The weights Ww | bw are split into the wave's 18 B-operand registers x 4 once per wave (workgroups are persistent over
-// pairs); the basis rows are split per tile.
-
+// ---------------------------------------------------------------------------------------------------- bf16x3 helpers
+// The per-edge filter  w_e = rbf_e Ww + bw  (K = B + 1 <= 32 -> 3F = 384 columns, 15 kflop per edge: 85 % of the message
+// step's arithmetic) runs on the matrix pipe in the tile kernels instead of 60 FMAs per lane and edge on the VALU.
+// FP32-exact as in csrc/mp_cfconv.hip: both operands are split into three bf16 pieces (8 + 8 + 8 mantissa bits, every
+// difference exact in FP32) and the six leading cross products run on v_mfma_f32_32x32x16_bf16 with FP32 accumulation (the
+// dropped products are below 2^-24 of |a||b|, the rounding of one FP32 product).
 __device__ __forceinline__ void split3_into(float x, bf16x8& hi, bf16x8& mid, bf16x8& lo, int i) {
   const __bf16 p0 = static_cast<__bf16>(x);
   const float r1 = x - static_cast<float>(p0);
@@ -453,56 +417,6 @@ __device__ __forceinline__ floatx16 mfma_bf16x3(const bf16x8 (&qa)[3], const bf1
   return acc;
 }
 
-// B operands of the filter GEMM for this lane: column f0 of part p, k = 16 ks + 8 (lane >> 5) + i; row B is the bias.
-// Every load is unconditional from a clamped address and masked afterwards (a conditional load costs a branch and a
-// full wait per load in hipcc's output).
-template <int BT>
-__device__ __forceinline__ void painn_filter_operands(const float* __restrict__ Ww, const float* __restrict__ bw, int B,
-                                                      int f0, int hh, bf16x8 (&wb)[3][2][3]) {
-  const float* bwp = bw != nullptr ? bw : Ww;       // any readable address; masked by has_b
-  const float has_b = bw != nullptr ? 1.0f : 0.0f;
-#pragma unroll
-  for (int p = 0; p < 3; ++p) {
-    const float bias = bwp[p * F + f0] * has_b;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int k = 16 * ks + 8 * hh + i;
-        if (BT > 0 && 16 * ks + i > BT) {             // beyond the bias slot for both lane halves: compile-time zero
-          split3_into(0.0f, wb[p][ks][0], wb[p][ks][1], wb[p][ks][2], i);
-          continue;
-        }
-        const int kc = k < B ? k : B - 1;
-        const float w = Ww[static_cast<int64_t>(kc) * 3 * F + p * F + f0];
-        // masks, not selects: a select lets the compiler sink the load into a branch
-        const float x = w * (k < B ? 1.0f : 0.0f) + bias * (k == B ? 1.0f : 0.0f);
-        split3_into(x, wb[p][ks][0], wb[p][ks][1], wb[p][ks][2], i);
-      }
-  }
-}
-
-// A operand of one basis tile for this lane: row = edge `er` (valid or not), k = 16 ks + 8 hh + i; slot k == B holds 1.
-template <int BT>
-__device__ __forceinline__ void painn_basis_load(const float* __restrict__ rbf, int B, int64_t er, int hh, float (&ra)[2][8]) {
-  if constexpr (BT == 20) {   // 80-B rows: 16-B pieces
-    const float4* rp = reinterpret_cast<const float4*>(rbf + er * 20);
-    const float4 t0 = rp[2 * hh], t1 = rp[2 * hh + 1], t2 = rp[4];
-    ra[0][0] = t0.x; ra[0][1] = t0.y; ra[0][2] = t0.z; ra[0][3] = t0.w;
-    ra[0][4] = t1.x; ra[0][5] = t1.y; ra[0][6] = t1.z; ra[0][7] = t1.w;
-    ra[1][0] = t2.x; ra[1][1] = t2.y; ra[1][2] = t2.z; ra[1][3] = t2.w;
-    ra[1][4] = 1.0f; ra[1][5] = 0.0f; ra[1][6] = 0.0f; ra[1][7] = 0.0f;
-  } else {
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int k = 16 * ks + 8 * hh + i;
-        const float x = rbf[er * B + (k < B ? k : B - 1)];
-        ra[ks][i] = k < B ? x : (k == B ? 1.0f : 0.0f);
-      }
-  }
-}
 template <int BT>
 __device__ __forceinline__ void painn_basis_split(const float (&ra)[2][8], bool valid, int hh, bf16x8 (&qa)[2][3]) {
 #pragma unroll
@@ -515,155 +429,28 @@ __device__ __forceinline__ void painn_basis_split(const float (&ra)[2][8], bool 
     }
 }
 
-template <int BT, bool PERM, bool ENV>
-__global__ __launch_bounds__(256, 2) void painn_message_mfma_kernel(PainnMsgArgs a) {
-  constexpr int EB = 4;     // sender rows in flight per lane: 4 x 10 loads, well inside the 6-bit vmcnt (63)
-  const int lane = threadIdx.x & 63;
-  const int fq = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
-  const int hh = lane >> 5, c = lane & 31;
-  const int B = BT > 0 ? BT : a.B;
-  const int f0 = 32 * fq + c;
-  const int rm = (c & 3) + 4 * (c >> 3), hm = (c >> 2) & 1;   // A row c = edge rm of lane half hm
-  const int M = static_cast<int>(a.M), N = static_cast<int>(a.N);
-  const int npairs = (N + 1) >> 1;
-  int pr = static_cast<int>(mp_xcd_block(blockIdx.x, gridDim.x));
-  // first pair's edge range requested before the weights, so both fly together
-  int n = 2 * pr + hh;
-  int nc = n < N ? n : N - 1;
-  int e_lo = a.ptr[nc], e_hi = a.ptr[nc + 1];
-  bf16x8 wb[3][2][3];
-  painn_filter_operands<BT>(a.Ww, a.bw, B, f0, hh, wb);
-  for (; pr < npairs; pr += static_cast<int>(gridDim.x)) {
-    const bool has = n < N;
-    e_lo = e_lo < 0 ? 0 : (e_lo > M ? M : e_lo);
-    e_hi = e_hi < e_lo ? e_lo : (e_hi > M ? M : e_hi);
-    const int cnt = has ? e_hi - e_lo : 0;
-    const int lo0 = __builtin_amdgcn_readlane(e_lo, 0), lo1 = __builtin_amdgcn_readlane(e_lo, 32);
-    const int cnt0 = __builtin_amdgcn_readlane(cnt, 0), cnt1 = __builtin_amdgcn_readlane(cnt, 32);
-    const int maxc = cnt0 > cnt1 ? cnt0 : cnt1;
-    const int n_this = n;
-    // next pair's edge range: in flight under this pair's work
-    n = 2 * (pr + static_cast<int>(gridDim.x)) + hh;
-    nc = n < N ? n : N - 1;
-    const int nx_lo = a.ptr[nc], nx_hi = a.ptr[nc + 1];
-    float ds = 0.0f, dv[3] = {0.0f, 0.0f, 0.0f};
-    for (int cb = 0; cb < maxc; cb += 16) {
-      // ---- phase A: sender ids of this lane half's 16 edges (register order; past the end: the receiver's last edge,
-      //      whose filter row is 0) and the basis tile's row c - all requested together
-      int jr[16], er[16];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        int slot = e_lo + (cb + r < cnt ? cb + r : (cnt > 0 ? cnt - 1 : 0));
-        slot = slot < M ? slot : M - 1;
-        er[r] = PERM ? a.perm[slot] : slot;
-      }
-#pragma unroll
-      for (int r = 0; r < 16; ++r) jr[r] = a.send[er[r]];
-      const int lo_m = hm ? lo1 : lo0, cnt_m = hm ? cnt1 : cnt0;
-      const bool rv = cb + rm < cnt_m;
-      int slot_m = lo_m + (rv ? cb + rm : 0);
-      slot_m = slot_m < M ? slot_m : M - 1;
-      const int64_t er_m = PERM ? a.perm[slot_m] : slot_m;
-      float ra[2][8];
-      painn_basis_load<BT>(a.rbf, B, er_m, hh, ra);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int r = 0; r < 16; ++r) jr[r] = jr[r] < 0 ? 0 : (jr[r] >= N ? N - 1 : jr[r]);
-      // ---- phase B: the first batch of sender rows goes out before the matrix work, so that it flies under it
-      float sj[EB][3], vj[EB][3], rr[EB][3], ev[EB];
-      auto request = [&](int bt) {
-#pragma unroll
-        for (int u = 0; u < EB; ++u) {
-
-          const float* srow = a.s + static_cast<int64_t>(jr[bt + u]) * 3 * F + f0;
-          const float* vrow = a.v + static_cast<int64_t>(jr[bt + u]) * 3 * F + f0;
-#pragma unroll
-          for (int p = 0; p < 3; ++p) {
-            sj[u][p] = srow[p * F];
-            vj[u][p] = vrow[p * F];
-            rr[u][p] = a.rij[static_cast<int64_t>(er[bt + u]) * 3 + p];
-          }
-          ev[u] = ENV ? a.env[er[bt + u]] : 1.0f;
-        }
-      };
-      request(0);
-      __builtin_amdgcn_sched_barrier(0);
-      // ---- phase C: filter tile on the matrix pipe
-      bf16x8 qa[2][3];
-      painn_basis_split<BT>(ra, rv, hh, qa);
-      floatx16 acc[3];
-#pragma unroll
-      for (int p = 0; p < 3; ++p) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[p][r] = 0.0f;
-        acc[p] = mfma_bf16x3(qa[0], wb[p][0], acc[p]);
-        acc[p] = mfma_bf16x3(qa[1], wb[p][1], acc[p]);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      // ---- phase D: messages in edge order
-#pragma unroll
-      for (int bt = 0; bt < 16; bt += EB) {
-        if (bt > 0) {
-          if (bt >= maxc - cb) break;   // wave-uniform: neither half has edges in this batch
-          request(bt);
-        }
-#pragma unroll
-        for (int u = 0; u < EB; ++u) {
-          float sw[3];
-#pragma unroll
-          for (int p = 0; p < 3; ++p) {
-            float wv_ = acc[p][bt + u];                   // Dense: x W + b (bias = k slot B)
-            if (ENV) wv_ *= ev[u];                         // lay_mult_cutoff([w, envelope])
-            sw[p] = sj[u][p] * wv_;                        // lay_mult([s, w])
-          }
-          ds += sw[0];
-#pragma unroll
-          for (int k = 0; k < 3; ++k) dv[k] += sw[1] * vj[u][k] + sw[2] * rr[u][k];   // (sw2 * v_j) + (sw3 * r_ij)
-        }
-      }
-    }
-    if (has) {
-      if (a.z_in) {   // residual adds of PAiNN.py:126-127 fused: z + ds, v + dv
-        ds += a.z_in[static_cast<int64_t>(n_this) * F + f0];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) dv[k] += a.v[(static_cast<int64_t>(n_this) * 3 + k) * F + f0];
-      }
-      a.ds[static_cast<int64_t>(n_this) * F + f0] = ds;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) a.dv[(static_cast<int64_t>(n_this) * 3 + k) * F + f0] = dv[k];
-    }
-    e_lo = nx_lo;
-    e_hi = nx_hi;
-  }
-}
-
-template <int BT>
-void launch_message_mfma(const PainnMsgArgs& a, unsigned blocks, hipStream_t st) {
-  if (a.perm != nullptr) {
-    if (a.env != nullptr) painn_message_mfma_kernel<BT, true, true><<<blocks, 256, 0, st>>>(a);
-    else painn_message_mfma_kernel<BT, true, false><<<blocks, 256, 0, st>>>(a);
-  } else {
-    if (a.env != nullptr) painn_message_mfma_kernel<BT, false, true><<<blocks, 256, 0, st>>>(a);
-    else painn_message_mfma_kernel<BT, false, false><<<blocks, 256, 0, st>>>(a);
-  }
-}
-
 // ---------------------------------------------------------------------------------------------------- message, tiles
-// The production form of the matrix-pipe message step: node TILES staged in LDS.  Measured on the kernel above (config 3):
-// what bounds the message step is not arithmetic but the vector-memory pipe - every edge pulls its sender's s_j and v_j
-// rows (3 KB) through the CU's L1, 62 MB per launch, and every wave re-reads the filter weights - with the phases of all
-// waves in step (all load, then all compute).  Batched molecular graphs have no edge between graphs, so the senders of a
-// range of receivers lie inside the receivers' own graph: a workgroup takes a tile = a few consecutive receivers of ONE
-// graph and stages
+// The matrix-pipe message step: node TILES staged in LDS.  What bounds the message step is not arithmetic but the
+// vector-memory pipe - in a gather form every edge pulls its sender's s_j and v_j rows (3 KB) through the CU's L1, 62 MB
+// per launch at config 3, and every wave re-reads the filter weights - with the phases of all waves in step (all load,
+// then all compute).  Batched molecular graphs have no edge between graphs, so the senders of a range of receivers lie
+// inside the receivers' own graph: a workgroup takes a tile = a few consecutive receivers of ONE graph and stages
 //   * the s and v rows of the whole graph (1.5 KB + 1.5 KB per node, contiguous in memory) by LDS-DMA
 //     (global_load_lds_dwordx4: 1 KB per wave instruction, no registers, each byte crosses L1 once per tile), and
 //   * the tile's edge data - basis rows, unit vectors, sender ids, envelope: contiguous too, the edge list being
 //     receiver-sorted - through registers;
-// after ONE barrier the tile runs from LDS: filter on the matrix pipe exactly as above (A rows from the LDS basis rows,
-// B operands = the wave's slice of a pre-split bf16 image of Ww | bw, mp_painn_filter_pack_f32, 18 x 16 B per lane), the
-// sender rows by ds_read_b32 (lane = feature: conflict-free).  The tile table (receivers, graph node range, edge range per
-// tile) is built once per bound batch by the host (gcnn_keras_amd/fused_painn.py).  Unsorted edge lists (perm) and graphs
-// whose rows do not fit LDS keep the gather kernels above.
+// after ONE barrier the tile runs from LDS.  The four waves serve a PAIR of receivers at a time, wave q the feature quarter
+// 32 q .. 32 q + 31 of all three filter parts.  One MFMA tile = 32 edge rows x 32 features: the accumulator leaves rows
+// {0-3, 8-11, 16-19, 24-27} in lanes 0-31 and rows {4-7, 12-15, ...} in lanes 32-63, sixteen rows per lane - so lane half h
+// is given the edges of receiver 2 pair + h (row m of the A operand = edge (m & 3) + 4 (m >> 3) of the half (m >> 2) & 1),
+// and each half walks ITS receiver's edges in register order = edge order (the order of tf.math.segment_sum after the
+// stable sort: deterministic, no atomics, no cross-lane step at all).  A rows come from the LDS basis rows with 1 in the
+// bias slot k = B; rows beyond a receiver's edge count are zero (bias slot included), so their filter - and message - is
+// exactly 0 and their reads repeat a valid edge.  B operands = the wave's slice of a pre-split bf16 image of Ww | bw
+// (mp_painn_filter_pack_f32, 18 x 16 B per lane); the sender rows by ds_read_b32 (lane = feature: conflict-free).  The tile
+// table (receivers, graph node range, edge range per tile) is built once per bound batch by the host
+// (gcnn_keras_amd/fused_painn.py).  Unsorted edge lists (perm) and graphs whose rows do not fit LDS keep the gather kernels
+// above.
 struct PainnTileArgs {
   const float* s;        // (N, 3F)
   const float* v;        // (N, 3, F)
@@ -1030,8 +817,8 @@ __global__ __launch_bounds__(256) void painn_message_bwd_kernel(PainnMsgBwdArgs 
 #pragma unroll
             for (int q = 0; q < MAXB / 2; ++q) {
               if (2 * q < B) {
-                const floatx2 x0 = {readlane_f(meta[u], 2 * q), readlane_f(metad[u], 2 * q)};
-                const floatx2 x1 = {readlane_f(meta[u], 2 * q + 1), readlane_f(metad[u], 2 * q + 1)};
+                const floatx2 x0 = {mp_bcast(meta[u], 2 * q), mp_bcast(metad[u], 2 * q)};
+                const floatx2 x1 = {mp_bcast(meta[u], 2 * q + 1), mp_bcast(metad[u], 2 * q + 1)};
 #pragma unroll
                 for (int p = 0; p < 3; ++p) {
                   pk_fma_wlo(ff[p], x0, wp[p][q]);
@@ -1042,11 +829,11 @@ __global__ __launch_bounds__(256) void painn_message_bwd_kernel(PainnMsgBwdArgs 
             const float f[3] = {ff[0].x, ff[1].x, ff[2].x}, fd[3] = {ff[0].y, ff[1].y, ff[2].y};
             float rk[3];
 #pragma unroll
-            for (int k = 0; k < 3; ++k) rk[k] = readlane_f(meta[u], B + k);
+            for (int k = 0; k < 3; ++k) rk[k] = mp_bcast(meta[u], B + k);
             // filter and its derivative w.r.t. the distance (the envelope is a second factor: product rule)
             float wf[3], wd[3];
-            const float envv = a.env ? readlane_f(meta[u], B + 3) : 1.0f;
-            const float envdv = (a.env && a.envd) ? readlane_f(metad[u], B) : 0.0f;
+            const float envv = a.env ? mp_bcast(meta[u], B + 3) : 1.0f;
+            const float envdv = (a.env && a.envd) ? mp_bcast(metad[u], B) : 0.0f;
 #pragma unroll
             for (int p = 0; p < 3; ++p) {
               const float wx = f[p] + bias[p];
@@ -1164,11 +951,6 @@ __device__ __forceinline__ float fold4(bool bit, float x, float y) {   // partne
   int t = __builtin_amdgcn_update_dpp(0, __float_as_int(send), 0x104, 0xf, 0x5, false);
   t = __builtin_amdgcn_update_dpp(t, __float_as_int(send), 0x114, 0xf, 0xA, false);
   return keep + __int_as_float(t);
-}
-__device__ __forceinline__ float xor4_sum(float x) {                   // x[l] + x[l ^ 4]
-  int t = __builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x104, 0xf, 0x5, false);
-  t = __builtin_amdgcn_update_dpp(t, __float_as_int(x), 0x114, 0xf, 0xA, false);
-  return x + __int_as_float(t);
 }
 // NV = 8, 16 or 32 values per lane -> every lane c of a 32-lane half holds the half's total of value
 // v(c) = bit4(c) + 2 bit3(c) + 4 bit2(c) [+ 8 bit1(c) [+ 16 bit0(c)]]: each exchange-add halves the number of live values
@@ -1512,101 +1294,6 @@ __global__ __launch_bounds__(256, 2) void painn_message_bwd_tile_kernel(PainnBwd
   }
 }
 
-// ---------------------------------------------------------------------------------------------------- update, node side
-// uv (3N, 2F): row (n,k) = [v_u | v_v] of component k (one GEMM with the concatenated kernels [Wu | Wv]).
-// pre:  c (N, 2F) = [z' | sqrt(relu(sum_k v_v^2))]  (EuclideanNorm(axis=2), geom.py:181-193; LazyConcatenate),
-//       prod (N, F) = sum_k v_u v_v                   (ScalarProduct(axis=2), geom.py:261)
-__global__ void painn_update_pre_kernel(const float* __restrict__ zp, const float* __restrict__ uv, int64_t N,
-                                        float* __restrict__ c, float* __restrict__ prod) {
-  const int64_t total = N * F;
-  const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
-  for (int64_t t = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; t < total; t += stride) {
-    const int64_t n = t / F;
-    const int f = static_cast<int>(t % F);
-    float pr = 0.0f, sq = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const float vu = uv[((n * 3 + k) * 2) * F + f];
-      const float vv = uv[((n * 3 + k) * 2 + 1) * F + f];
-      pr += vu * vv;
-      sq += vv * vv;
-    }
-    c[n * 2 * F + f] = zp[t];
-    c[n * 2 * F + F + f] = sqrtf(fmaxf(sq, 0.0f));
-    prod[t] = pr;
-  }
-}
-
-// post: z'' = z' + prod a_sv + a_ss ; v''[k] = v'[k] + a_vv v_u[k]     (painn_conv.py:208-213 + PAiNN.py:131-132)
-__global__ void painn_update_post_kernel(const float* __restrict__ zp, const float* __restrict__ vp,
-                                         const float* __restrict__ uv, const float* __restrict__ prod,
-                                         const float* __restrict__ a, int64_t N, float* __restrict__ z2,
-                                         float* __restrict__ v2) {
-  const int64_t total = N * F;
-  const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
-  for (int64_t t = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; t < total; t += stride) {
-    const int64_t n = t / F;
-    const int f = static_cast<int>(t % F);
-    const float a_vv = a[n * 3 * F + f], a_sv = a[n * 3 * F + F + f], a_ss = a[n * 3 * F + 2 * F + f];
-    z2[t] = zp[t] + (prod[t] * a_sv + a_ss);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const float vu = uv[((n * 3 + k) * 2) * F + f];
-      v2[(n * 3 + k) * F + f] = vp[(n * 3 + k) * F + f] + a_vv * vu;
-    }
-  }
-}
-
-// reverse of post: g_a (N,3F) = [sum_k g_v2[k] v_u[k] | g_z2 prod | g_z2],  g_prod (N,F) = g_z2 a_sv
-__global__ void painn_update_post_bwd_kernel(const float* __restrict__ gz2, const float* __restrict__ gv2,
-                                             const float* __restrict__ uv, const float* __restrict__ prod,
-                                             const float* __restrict__ a, int64_t N, float* __restrict__ g_a,
-                                             float* __restrict__ g_prod) {
-  const int64_t total = N * F;
-  const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
-  for (int64_t t = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; t < total; t += stride) {
-    const int64_t n = t / F;
-    const int f = static_cast<int>(t % F);
-    float gavv = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) gavv += gv2[(n * 3 + k) * F + f] * uv[((n * 3 + k) * 2) * F + f];
-    const float g = gz2[t];
-    g_a[n * 3 * F + f] = gavv;
-    g_a[n * 3 * F + F + f] = g * prod[t];
-    g_a[n * 3 * F + 2 * F + f] = g;
-    g_prod[t] = g * a[n * 3 * F + F + f];
-  }
-}
-
-// reverse of pre (+ the v_u part of post): with g_c (N,2F) = dE/dc,
-//   g_zp = g_z2 + g_c[:, :F]
-//   g_vu[k] = g_v2[k] a_vv + g_prod v_v[k] ;  g_vv[k] = g_prod v_u[k] + g_c[:, F:] v_v[k] / ||v_v||   (0 at the cusp)
-__global__ void painn_update_pre_bwd_kernel(const float* __restrict__ gz2, const float* __restrict__ gv2,
-                                            const float* __restrict__ uv, const float* __restrict__ c,
-                                            const float* __restrict__ a, const float* __restrict__ g_prod,
-                                            const float* __restrict__ g_c, int64_t N, float* __restrict__ g_zp,
-                                            float* __restrict__ g_uv) {
-  const int64_t total = N * F;
-  const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
-  for (int64_t t = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; t < total; t += stride) {
-    const int64_t n = t / F;
-    const int f = static_cast<int>(t % F);
-    const float nrm = c[n * 2 * F + F + f];
-    const float gn = g_c[n * 2 * F + F + f];
-    const float gp = g_prod[t];
-    const float a_vv = a[n * 3 * F + f];
-    const float inv = nrm > 0.0f ? gn / nrm : 0.0f;   // d sqrt(s) = v_v / sqrt(s); zero sub-gradient at s = 0
-    g_zp[t] = gz2[t] + g_c[n * 2 * F + f];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const float vu = uv[((n * 3 + k) * 2) * F + f];
-      const float vv = uv[((n * 3 + k) * 2 + 1) * F + f];
-      g_uv[((n * 3 + k) * 2) * F + f] = gv2[(n * 3 + k) * F + f] * a_vv + gp * vv;
-      g_uv[((n * 3 + k) * 2 + 1) * F + f] = gp * vu + inv * vv;
-    }
-  }
-}
-
 // ---------------------------------------------------------------------------------------------------- geometry, backward
 // dE/dx_n = sum_{e: recv = n} t_e - sum_{e: send = n} t_e,  t_e = g_d r_ij + (g_r - (g_r . r_ij) r_ij) / d
 // (d = |x_i - x_j|, r_ij = (x_i - x_j) / d with divide_no_nan: no contribution at d = 0); g_d / g_rij arrive as `slices`
@@ -1653,25 +1340,13 @@ __global__ __launch_bounds__(256) void painn_geometry_bwd_kernel(const float* __
       }
     }
 #pragma unroll
-    for (int k = 0; k < 3; ++k) acc[k] = wave_sum(acc[k]);
+    for (int k = 0; k < 3; ++k) acc[k] = mp_wave_sum(acc[k]);
     if (lane == 0) {
       gx[n * 3 + 0] = scale * acc[0];
       gx[n * 3 + 1] = scale * acc[1];
       gx[n * 3 + 2] = scale * acc[2];
     }
   }
-}
-
-// MPENGINE_PAINN_MFMA_GATHER=1 routes mp_painn_message_f32 to painn_message_mfma_kernel (filter on the matrix pipe, sender
-// rows gathered from global memory): measured 19.9 us against 16.2 us for the VALU build at config 3 - what the MFMAs save
-// in vector issue this form loses to its serial phases at two waves per SIMD - so it is an experiment, not the default.  The
-// default matrix-pipe route is the LDS tile kernel behind mp_painn_message_tiles_f32.
-bool painn_mfma_gather() {
-  static const bool v = [] {
-    const char* e = getenv("MPENGINE_PAINN_MFMA_GATHER");
-    return e != nullptr && e[0] == '1';
-  }();
-  return v;
 }
 
 }  // namespace
@@ -1730,12 +1405,6 @@ int mp_painn_message_f32(const float* s, const float* v, int64_t N, const float*
   MP_REQUIRE(dv != v, "mp_painn_message_f32: dv must not alias v (other waves still gather v)");
   PainnMsgArgs a{s, v, rbf, env, rij, Ww, bw, ptr, perm, send, z_in, ds, dv, N, M, B};
   hipStream_t st = mp::as_stream(stream);
-  if (B == 20 && M > 0 && painn_mfma_gather()) {   // opt-in experiment (see painn_mfma_gather), 20-function basis build only
-    int64_t blocks = (N + 1) / 2;                    // a workgroup per receiver pair, persistent beyond two per CU
-    if (blocks > 512) blocks = 512;
-    launch_message_mfma<20>(a, static_cast<unsigned>(blocks), st);   // (the generic-basis build of this form spills)
-    return mp::check_launch("mp_painn_message_f32");
-  }
   int64_t blocks = mp::ceil_div(2 * N, 4);   // two waves (feature halves) per node, four waves per workgroup
   if (blocks > 4096) blocks = 4096;
   if (B == 20) painn_message_kernel<20><<<static_cast<unsigned>(blocks), 256, 0, st>>>(a);
@@ -1873,44 +1542,6 @@ int mp_painn_message_bwd_f32(const float* s, const float* v, int64_t N, const fl
   if (B == 20) painn_message_bwd_kernel<20><<<static_cast<unsigned>(blocks), 256, 0, st>>>(a);
   else painn_message_bwd_kernel<0><<<static_cast<unsigned>(blocks), 256, 0, st>>>(a);
   return mp::check_launch("mp_painn_message_bwd_f32");
-}
-
-int mp_painn_update_pre_f32(const float* zp, const float* uv, int64_t N, float* c, float* prod, mpStream_t stream) {
-  MP_REQUIRE(N >= 0, "mp_painn_update_pre_f32: bad size");
-  if (N == 0) return MP_OK;
-  MP_REQUIRE(zp && uv && c && prod, "mp_painn_update_pre_f32: null pointer");
-  painn_update_pre_kernel<<<mp::grid_for(N * F), 256, 0, mp::as_stream(stream)>>>(zp, uv, N, c, prod);
-  return mp::check_launch("mp_painn_update_pre_f32");
-}
-
-int mp_painn_update_post_f32(const float* zp, const float* vp, const float* uv, const float* prod, const float* a,
-                             int64_t N, float* z2, float* v2, mpStream_t stream) {
-  MP_REQUIRE(N >= 0, "mp_painn_update_post_f32: bad size");
-  if (N == 0) return MP_OK;
-  MP_REQUIRE(zp && vp && uv && prod && a && z2 && v2, "mp_painn_update_post_f32: null pointer");
-  painn_update_post_kernel<<<mp::grid_for(N * F), 256, 0, mp::as_stream(stream)>>>(zp, vp, uv, prod, a, N, z2, v2);
-  return mp::check_launch("mp_painn_update_post_f32");
-}
-
-int mp_painn_update_post_bwd_f32(const float* g_z2, const float* g_v2, const float* uv, const float* prod,
-                                 const float* a, int64_t N, float* g_a, float* g_prod, mpStream_t stream) {
-  MP_REQUIRE(N >= 0, "mp_painn_update_post_bwd_f32: bad size");
-  if (N == 0) return MP_OK;
-  MP_REQUIRE(g_z2 && g_v2 && uv && prod && a && g_a && g_prod, "mp_painn_update_post_bwd_f32: null pointer");
-  painn_update_post_bwd_kernel<<<mp::grid_for(N * F), 256, 0, mp::as_stream(stream)>>>(g_z2, g_v2, uv, prod, a, N, g_a,
-                                                                                       g_prod);
-  return mp::check_launch("mp_painn_update_post_bwd_f32");
-}
-
-int mp_painn_update_pre_bwd_f32(const float* g_z2, const float* g_v2, const float* uv, const float* c, const float* a,
-                                const float* g_prod, const float* g_c, int64_t N, float* g_zp, float* g_uv,
-                                mpStream_t stream) {
-  MP_REQUIRE(N >= 0, "mp_painn_update_pre_bwd_f32: bad size");
-  if (N == 0) return MP_OK;
-  MP_REQUIRE(g_z2 && g_v2 && uv && c && a && g_prod && g_c && g_zp && g_uv, "mp_painn_update_pre_bwd_f32: null pointer");
-  painn_update_pre_bwd_kernel<<<mp::grid_for(N * F), 256, 0, mp::as_stream(stream)>>>(g_z2, g_v2, uv, c, a, g_prod, g_c,
-                                                                                      N, g_zp, g_uv);
-  return mp::check_launch("mp_painn_update_pre_bwd_f32");
 }
 
 int mp_edge_geometry_bwd_f32(const float* g_d, const float* g_rij, int slices, const float* rij, const float* dist,

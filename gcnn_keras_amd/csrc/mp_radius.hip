@@ -19,15 +19,6 @@
 
 namespace {
 
-__device__ __forceinline__ int64_t owner_of(const int64_t* __restrict__ splits, int64_t G, int64_t e) {
-  int64_t lo = 0, hi = G;
-  while (hi - lo > 1) {
-    int64_t mid = (lo + hi) >> 1;
-    if (splits[mid] <= e) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
 __device__ __forceinline__ float dist_f32(const float* __restrict__ xyz, int64_t a, int64_t b) {
   const float dx = xyz[a * 3 + 0] - xyz[b * 3 + 0];
   const float dy = xyz[a * 3 + 1] - xyz[b * 3 + 1];
@@ -61,7 +52,7 @@ __global__ void radius_graph_kernel(const float* __restrict__ xyz, const int64_t
                                     float* __restrict__ dist) {
   const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
   for (int64_t a = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; a < N; a += stride) {
-    const int64_t g = owner_of(node_splits, G, a);
+    const int64_t g = mp_owner_of(node_splits, G, a);
     const int64_t base = node_splits[g];
     const int64_t n = node_splits[g + 1] - base;
     const int64_t i = a - base;
@@ -92,7 +83,6 @@ __global__ void edge_splits_kernel(const int32_t* __restrict__ node_ptr, const i
     edge_splits[g] = node_ptr[node_splits[g]];
 }
 
-inline size_t align256(size_t x) { return (x + 255) & ~static_cast<size_t>(255); }
 
 }  // namespace
 
@@ -108,7 +98,7 @@ int mp_radius_graph_workspace_bytes(int64_t N, size_t* bytes_out_host) {
     mp::set_error("rocprim temp-size query failed: %s", hipGetErrorString(e));
     return MP_EHIP;
   }
-  *bytes_out_host = align256(temp) + align256(sizeof(int32_t) * static_cast<size_t>(N + 1));
+  *bytes_out_host = mp::align256(temp) + mp::align256(sizeof(int32_t) * static_cast<size_t>(N + 1));
   return MP_OK;
 }
 
@@ -123,8 +113,8 @@ int mp_radius_graph_count_f32(const float* xyz, const int64_t* node_splits, int6
   MP_REQUIRE(ws_bytes >= need, "mp_radius_graph_count_f32: workspace %zu < %zu bytes", ws_bytes, need);
   hipStream_t s = mp::as_stream(stream);
   int32_t* counts = static_cast<int32_t*>(ws);
-  void* temp = static_cast<char*>(ws) + align256(sizeof(int32_t) * static_cast<size_t>(N + 1));
-  size_t temp_bytes = ws_bytes - align256(sizeof(int32_t) * static_cast<size_t>(N + 1));
+  void* temp = static_cast<char*>(ws) + mp::align256(sizeof(int32_t) * static_cast<size_t>(N + 1));
+  size_t temp_bytes = ws_bytes - mp::align256(sizeof(int32_t) * static_cast<size_t>(N + 1));
   MP_HIP(hipMemsetAsync(counts, 0, sizeof(int32_t) * static_cast<size_t>(N + 1), s));
   if (N > 0) {
     MP_REQUIRE(xyz && node_splits && G > 0, "mp_radius_graph_count_f32: null pointer / no graphs");

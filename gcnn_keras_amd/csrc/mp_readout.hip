@@ -117,7 +117,7 @@ __global__ __launch_bounds__(256) void pool_mlp2_kernel(const float* __restrict_
       o += mp_apply_act(act0, alpha0, pre) * w1v[h];
       cv[h] = w1v[h] * mp_act_grad(act0, alpha0, pre);   // dE / d pre-activation of this lane's hidden units
     }
-    for (int off = 32; off > 0; off >>= 1) o += __shfl_xor(o, off, 64);
+    o = mp_wave_sum(o);
     if (lane == 0) out[g] = o + b1v;
     if (g_x) {
       float gp[NK];

@@ -17,7 +17,6 @@
 
 namespace {
 
-inline size_t align256(size_t n) { return (n + 255) & ~static_cast<size_t>(255); }
 
 __device__ __forceinline__ int64_t rel_of(const int64_t* rel, int64_t r, int64_t nrel) {
   const int64_t v = rel[r];
@@ -133,7 +132,7 @@ int mp_relational_dense_wgrad_ws_bytes(int64_t R, int64_t nrel, size_t* bytes_ou
   int rc = mp_sort_workspace_bytes(R, &sort);
   if (rc != MP_OK) return rc;
   const size_t n = static_cast<size_t>(R > 0 ? R : 1);
-  *bytes_out_host = 3 * align256(sizeof(int32_t) * n) + align256(sizeof(int32_t) * static_cast<size_t>(nrel + 2)) + sort;
+  *bytes_out_host = 3 * mp::align256(sizeof(int32_t) * n) + mp::align256(sizeof(int32_t) * static_cast<size_t>(nrel + 2)) + sort;
   return MP_OK;
 }
 
@@ -160,12 +159,12 @@ int mp_relational_dense_wgrad_f32(const float* x, int64_t R, int64_t K, const in
   if (rc != MP_OK) return rc;
   MP_REQUIRE(ws_bytes >= need, "mp_relational_dense_wgrad_f32: workspace %zu < %zu bytes", ws_bytes, need);
   char* p = static_cast<char*>(ws);
-  const size_t nb = align256(sizeof(int32_t) * static_cast<size_t>(R));
+  const size_t nb = mp::align256(sizeof(int32_t) * static_cast<size_t>(R));
   int32_t* ids = reinterpret_cast<int32_t*>(p);
   int32_t* ids_sorted = reinterpret_cast<int32_t*>(p + nb);
   int32_t* perm = reinterpret_cast<int32_t*>(p + 2 * nb);
   int32_t* ptr = reinterpret_cast<int32_t*>(p + 3 * nb);
-  const size_t head = 3 * nb + align256(sizeof(int32_t) * static_cast<size_t>(nrel + 2));
+  const size_t head = 3 * nb + mp::align256(sizeof(int32_t) * static_cast<size_t>(nrel + 2));
   rel_ids_kernel<<<mp::grid_for(R), 256, 0, s>>>(rel, R, nrel, ids);
   rc = mp::check_launch("mp_relational_dense_wgrad_f32 (ids)");
   if (rc != MP_OK) return rc;

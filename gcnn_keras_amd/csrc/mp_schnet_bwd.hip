@@ -178,11 +178,6 @@ __global__ __launch_bounds__(256, HEAD ? 1 : 2) void schnet_bwd_chain_kernel(Bwd
   }
 }
 
-__device__ __forceinline__ float wave_sum_f(float v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // out_n = scale * dE/dx_n with dE/dx_n = sum over the edges that touch n of g_d[e] (x_n - x_other) / d_e
 // (d = |x_recv - x_send|: the same expression on the receiver and on the sender side; divide_no_nan - nothing at d = 0).
 // One wave per node, lanes stride the node's receiver-side and sender-side edge lists (CSR offsets + the stable-sort
@@ -220,7 +215,7 @@ __global__ __launch_bounds__(256) void schnet_force_kernel(const float* __restri
       }
     }
 #pragma unroll
-    for (int k = 0; k < 3; ++k) acc[k] = wave_sum_f(acc[k]);
+    for (int k = 0; k < 3; ++k) acc[k] = mp_wave_sum(acc[k]);
     if (lane == 0) {
       out[n * 3 + 0] = scale * acc[0];
       out[n * 3 + 1] = scale * acc[1];

@@ -536,7 +536,7 @@ __global__ __launch_bounds__(256) void schnet_readout_kernel(const float* __rest
       }
     }
     float o = y * w1v;
-    for (int off = 32; off > 0; off >>= 1) o += __shfl_xor(o, off, 64);
+    o = mp_wave_sum(o);
     if (lane == 0) out[g] = o + (linear_head ? static_cast<float>(hi - lo) * b1v : b1v);
   }
 }

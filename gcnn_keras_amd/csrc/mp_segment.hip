@@ -197,7 +197,6 @@ __global__ void scatter_relational_kernel(int op, const float* __restrict__ edge
   }
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // dispatch of the three compile-time flags
 template <int W, typename PtrT>
@@ -226,7 +225,7 @@ int launch_segment_reduce(int op, const float* data, int64_t M, int64_t row_elem
                           const int32_t* perm, int64_t N_out, const float* weight, int normalize, float* out,
                           hipStream_t s, const char* what, const int32_t* row_index = nullptr, int64_t n_rows = 0,
                           int act = 0, float alpha = 0.0f) {
-  if (row_elems % 4 == 0 && aligned16(data) && aligned16(out)) {
+  if (row_elems % 4 == 0 && mp::aligned16(data) && mp::aligned16(out)) {
     launch_reduce_flags<4, PtrT>(mp::grid_for(N_out * (row_elems / 4)), s, op, data, M, row_elems, ptr, perm, N_out,
                                  weight, normalize, out, row_index, n_rows, act, alpha);
   } else {

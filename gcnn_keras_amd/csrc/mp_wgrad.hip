@@ -221,7 +221,7 @@ __global__ void softmax_rows_grad_kernel(const float* __restrict__ y, const floa
     const float* gr = g + r * C;
     float dot = 0.0f;
     for (int64_t c = lane; c < C; c += 64) dot += gr[c] * yr[c];
-    for (int o = 32; o > 0; o >>= 1) dot += __shfl_xor(dot, o, 64);
+    dot = mp_wave_sum(dot);
     for (int64_t c = lane; c < C; c += 64) out[r * C + c] = yr[c] * (gr[c] - dot);
   }
 }
@@ -237,7 +237,6 @@ __global__ void embedding_ids_kernel(const float* __restrict__ numbers, int64_t 
   }
 }
 
-inline size_t align256(size_t n) { return (n + 255) & ~static_cast<size_t>(255); }
 
 }  // namespace
 
@@ -307,7 +306,7 @@ int mp_embedding_grad_ws_bytes(int64_t N, int64_t vocab, size_t* bytes_out_host)
   int rc = mp_sort_workspace_bytes(N, &sort);
   if (rc != MP_OK) return rc;
   const size_t n = static_cast<size_t>(N > 0 ? N : 1);
-  *bytes_out_host = 3 * align256(sizeof(int32_t) * n) + align256(sizeof(int32_t) * static_cast<size_t>(vocab + 2)) + sort;
+  *bytes_out_host = 3 * mp::align256(sizeof(int32_t) * n) + mp::align256(sizeof(int32_t) * static_cast<size_t>(vocab + 2)) + sort;
   return MP_OK;
 }
 
@@ -327,13 +326,13 @@ int mp_embedding_grad_f32(const float* numbers, int64_t N, const float* g, int64
   MP_REQUIRE(ws_bytes >= need, "mp_embedding_grad_f32: workspace %zu < %zu bytes", ws_bytes, need);
   // stable sort by type + CSR + segment sum: rows of one type are added in node order
   char* p = static_cast<char*>(ws);
-  const size_t nb = align256(sizeof(int32_t) * static_cast<size_t>(N));
+  const size_t nb = mp::align256(sizeof(int32_t) * static_cast<size_t>(N));
   int32_t* ids = reinterpret_cast<int32_t*>(p);
   int32_t* ids_sorted = reinterpret_cast<int32_t*>(p + nb);
   int32_t* perm = reinterpret_cast<int32_t*>(p + 2 * nb);
   int32_t* ptr = reinterpret_cast<int32_t*>(p + 3 * nb);
-  void* sort_ws = p + 3 * nb + align256(sizeof(int32_t) * static_cast<size_t>(vocab + 2));
-  const size_t sort_bytes = ws_bytes - (3 * nb + align256(sizeof(int32_t) * static_cast<size_t>(vocab + 2)));
+  void* sort_ws = p + 3 * nb + mp::align256(sizeof(int32_t) * static_cast<size_t>(vocab + 2));
+  const size_t sort_bytes = ws_bytes - (3 * nb + mp::align256(sizeof(int32_t) * static_cast<size_t>(vocab + 2)));
   embedding_ids_kernel<<<mp::grid_for(N), 256, 0, s>>>(numbers, N, vocab, ids);
   rc = mp::check_launch("mp_embedding_grad_f32 (ids)");
   if (rc != MP_OK) return rc;

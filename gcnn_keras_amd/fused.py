@@ -286,10 +286,9 @@ class FusedSchnet:
             raise IndexError("edge index out of range for its graph")
         self.sorted = not (f & _ffi.MP_FLAG_UNSORTED_COL0)
         if not self.sorted and m > 0:
-            nbytes = ctypes.c_size_t(0)
-            _ffi.call("mp_sort_workspace_bytes", m, ctypes.byref(nbytes))
-            self.sort_ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-            self.sort_ws_bytes = nbytes.value
+            nbytes = _ffi.workspace_bytes("mp_sort_workspace_bytes", m)
+            self.sort_ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            self.sort_ws_bytes = nbytes
             self.recv_sorted = torch.empty(m, dtype=torch.int32, device=dev)
             self.perm = torch.empty(m, dtype=torch.int32, device=dev)
         splits = np.asarray(b["ns_host"])

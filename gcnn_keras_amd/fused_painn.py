@@ -240,8 +240,7 @@ class FusedPainn:
         if perm is not None or self.B > 31 or n == 0 or self.M == 0 or os.environ.get("MPENGINE_PAINN_TILES") == "0":
             return None
         # the CSR is read back once per bound batch: a few KB, next to the flag word bind reads anyway
-        tl = message_tile_table(node.row_splits_host(), ptr.cpu().numpy(), self.B,
-                                per=int(os.environ.get("MPENGINE_PAINN_TILE_R", "0")) or None, reverse=reverse)
+        tl = message_tile_table(node.row_splits_host(), ptr.cpu().numpy(), self.B, reverse=reverse)
         if tl is None:
             return None
         tl["table"] = torch.from_numpy(tl["table"]).to(node.values.device)

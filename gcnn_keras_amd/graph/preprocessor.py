@@ -5,8 +5,6 @@ and re-uploads the edge lists; here the whole batch goes through two kernels aro
 (csrc/mp_radius.hip).  Same rule: ``dist < max_distance`` AND among the ``max_neighbours + 1`` nearest entries of the
 row (exclusive mode), no self loops, row-major ``(i, j)`` order - hence receiver-sorted output.
 """
-import ctypes
-
 import torch
 
 from .. import _ffi
@@ -52,13 +50,12 @@ class SetRange:
         n, g = int(xyz.shape[0]), node_coordinates.nrows()
         md = -1.0 if self.max_distance is None else float(self.max_distance)
         mn = -1 if self.max_neighbours is None else int(min(self.max_neighbours, 2 ** 30))
-        nbytes = ctypes.c_size_t(0)
-        _ffi.call("mp_radius_graph_workspace_bytes", n, ctypes.byref(nbytes))
-        ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=xyz.device)
+        nbytes = _ffi.workspace_bytes("mp_radius_graph_workspace_bytes", n)
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=xyz.device)
         node_ptr = torch.empty(n + 1, dtype=torch.int32, device=xyz.device)
         edge_splits = torch.empty(g + 1, dtype=torch.int64, device=xyz.device)
         _ffi.call("mp_radius_graph_count_f32", _ffi.ptr(xyz), _ffi.ptr(node_coordinates.row_splits), g, n, md, mn,
-                  _ffi.ptr(node_ptr), _ffi.ptr(edge_splits), _ffi.ptr(ws), nbytes.value, _ffi.stream())
+                  _ffi.ptr(node_ptr), _ffi.ptr(edge_splits), _ffi.ptr(ws), nbytes, _ffi.stream())
         return edge_splits
 
     def _run(self, node_coordinates: RaggedTensor):
@@ -71,13 +68,12 @@ class SetRange:
         dev = xyz.device
         md = -1.0 if self.max_distance is None else float(self.max_distance)
         mn = -1 if self.max_neighbours is None else int(min(self.max_neighbours, 2 ** 30))
-        nbytes = ctypes.c_size_t(0)
-        _ffi.call("mp_radius_graph_workspace_bytes", n, ctypes.byref(nbytes))
-        ws = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, device=dev)
+        nbytes = _ffi.workspace_bytes("mp_radius_graph_workspace_bytes", n)
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
         node_ptr = torch.empty(n + 1, dtype=torch.int32, device=dev)
         edge_splits = torch.empty(g + 1, dtype=torch.int64, device=dev)
         _ffi.call("mp_radius_graph_count_f32", _ffi.ptr(xyz), _ffi.ptr(node_coordinates.row_splits), g, n, md, mn,
-                  _ffi.ptr(node_ptr), _ffi.ptr(edge_splits), _ffi.ptr(ws), nbytes.value, _ffi.stream())
+                  _ffi.ptr(node_ptr), _ffi.ptr(edge_splits), _ffi.ptr(ws), nbytes, _ffi.stream())
         m = int(node_ptr[-1].item())  # the output size is data dependent: one host read, as in the reference pipeline
         idx = torch.empty((m, 2), dtype=torch.int64, device=dev)
         cols = torch.empty((2, max(m, 1)), dtype=torch.int32, device=dev)

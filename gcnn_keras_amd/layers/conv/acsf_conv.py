@@ -79,17 +79,15 @@ class AcsfSpec:
         return out
 
     def grad(self, xyz, g):
-        import ctypes
         xyz, g = xyz.contiguous(), g.contiguous()
         dx = torch.empty((self.plan.N, 3), dtype=torch.float32, device=xyz.device)
-        nbytes = ctypes.c_size_t(0)
-        _ffi.call("mp_acsf_grad_ws_bytes", self.plan.M, self.K, ctypes.byref(nbytes))
-        ws = torch.empty((max(nbytes.value, 4) // 4,), dtype=torch.float32, device=xyz.device)
+        nbytes = _ffi.workspace_bytes("mp_acsf_grad_ws_bytes", self.plan.M, self.K)
+        ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.float32, device=xyz.device)
         csr = []
         for c in range(self.K):
             csr.extend(self._csr(c))
         name = "mp_acsf_g4_grad_f32" if self.g4 else "mp_acsf_g2_grad_f32"
-        _ffi.call(name, *self._head(xyz), *csr, *self._table(), _ffi.ptr(g), _ffi.ptr(ws), nbytes.value,
+        _ffi.call(name, *self._head(xyz), *csr, *self._table(), _ffi.ptr(g), _ffi.ptr(ws), nbytes,
                   _ffi.ptr(dx), _ffi.stream())
         return dx
 

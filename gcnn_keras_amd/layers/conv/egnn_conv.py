@@ -17,8 +17,6 @@ Reverse (forces): ``autograd.EgnnEdge``, first order.  A forward on the tape sto
 first layer's gradient per node over the CSRs of both index columns (``mp_segment_reduce_csr_f32``).  The weights are
 read in place and get no gradients: ``weights_need_grad`` tells the builder to step aside to the layer sequence.
 """
-import ctypes
-
 import torch
 
 from ... import _ffi
@@ -75,16 +73,15 @@ class EdgeStepSpec:
     def forward(self, pa, pb, x, save=False):
         n, e, f = self.plan.N, self.plan.M, FUSED_EDGE_SIZES["units"]
         ptr0, perm0, _ = self.plan.csr(0)
-        nbytes = ctypes.c_size_t(0)
-        _ffi.call("mp_egnn_edge_ws_bytes", e, ctypes.byref(nbytes))
-        ws = torch.empty((max(nbytes.value, 4) // 4,), dtype=torch.float32, device=pa.device)
+        nbytes = _ffi.workspace_bytes("mp_egnn_edge_ws_bytes", e)
+        ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.float32, device=pa.device)
         out = torch.empty((n, f), dtype=torch.float32, device=pa.device)
         z1 = torch.empty((e, f), dtype=torch.float32, device=pa.device) if save else None
         z2 = torch.empty((e, f), dtype=torch.float32, device=pa.device) if save else None
         _ffi.call("mp_egnn_edge_f32", _ffi.ptr(pa), _ffi.ptr(pb), n, _ffi.ptr(x), _ffi.ptr(self.plan.cols), e,
                   _ffi.ptr(ptr0), _ffi.ptr(perm0), _ffi.ptr(self.scales), self.dim_half, self.interleave, _ffi.ptr(self.wc),
                   _ffi.ptr(self.b1), self.act1, _ffi.ptr(self.w2), _ffi.ptr(self.b2), self.act2, _ffi.ptr(self.w_att),
-                  _ffi.ptr(self.b_att), self.act_att, self.alpha, _ffi.ptr(ws), nbytes.value, _ffi.ptr(z1),
+                  _ffi.ptr(self.b_att), self.act_att, self.alpha, _ffi.ptr(ws), nbytes, _ffi.ptr(z1),
                   _ffi.ptr(z2), _ffi.ptr(out), _ffi.stream())
         return (out, z1, z2) if save else out
 

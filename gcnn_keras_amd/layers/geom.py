@@ -324,16 +324,14 @@ class EdgeAngleSpec:
         return out
 
     def grad(self, v, g):
-        import ctypes
-        nbytes = ctypes.c_size_t(0)
-        _ffi.call("mp_edge_angle_grad_ws_bytes", self.plan.M, ctypes.byref(nbytes))
-        ws = torch.empty((max(nbytes.value, 4) // 4,), dtype=torch.float32, device=v.device)
+        nbytes = _ffi.workspace_bytes("mp_edge_angle_grad_ws_bytes", self.plan.M)
+        ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.float32, device=v.device)
         v_bar = torch.empty_like(v)
         ptr0, perm0, _ = self.plan.csr(0)
         ptr1, perm1, _ = self.plan.csr(1)
         _ffi.call("mp_edge_angle_grad_f32", _ffi.ptr(v), self.plan.N, _ffi.ptr(self.plan.cols), self.plan.M,
                   _ffi.ptr(ptr0), _ffi.ptr(perm0), _ffi.ptr(ptr1), _ffi.ptr(perm1), _ffi.ptr(self.scale),
-                  _ffi.ptr(g.contiguous()), _ffi.ptr(ws), nbytes.value, _ffi.ptr(v_bar), _ffi.stream())
+                  _ffi.ptr(g.contiguous()), _ffi.ptr(ws), nbytes, _ffi.ptr(v_bar), _ffi.stream())
         return v_bar
 
 

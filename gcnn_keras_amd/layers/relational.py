@@ -1,7 +1,5 @@
 """``RelationalDense`` (mirror of kgcnn/layers/relational.py:10-260 without ``num_bases`` / ``num_blocks``): a Dense layer
 with one kernel per relation, ``y = act(x W[rel] + b)``, on ``mp_relational_dense_f32`` (csrc/mp_relational.hip)."""
-import ctypes
-
 import torch
 
 from .. import _ffi
@@ -39,13 +37,12 @@ def relational_wgrad(x, g, rel, nrel, with_kernel=True, with_bias=True):
     rows = gc.numel() // max(u, 1)
     dw = torch.empty((nrel, k, u), dtype=torch.float32, device=g.device) if with_kernel else None
     db = torch.empty((u,), dtype=torch.float32, device=g.device) if with_bias else None
-    nbytes = ctypes.c_size_t(0)
-    ws = None
+    nbytes, ws = 0, None
     if with_kernel:
-        _ffi.call("mp_relational_dense_wgrad_ws_bytes", rows, nrel, ctypes.byref(nbytes))
-        ws = torch.empty((max(nbytes.value, 1),), dtype=torch.uint8, device=g.device)
+        nbytes = _ffi.workspace_bytes("mp_relational_dense_wgrad_ws_bytes", rows, nrel)
+        ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=g.device)
     _ffi.call("mp_relational_dense_wgrad_f32", _ffi.ptr(xc), rows, k, _ffi.ptr(rel), nrel, _ffi.ptr(gc), u,
-              _ffi.ptr(dw), _ffi.ptr(db), _ffi.ptr(ws), nbytes.value, _ffi.stream())
+              _ffi.ptr(dw), _ffi.ptr(db), _ffi.ptr(ws), nbytes, _ffi.stream())
     return dw, db
 
 

@@ -227,14 +227,12 @@ class IndexPlan:
         seg = self.col(k)
         perm = None
         if not assume_sorted and not self.is_sorted(k) and self.M > 0:
-            import ctypes
-            nbytes = ctypes.c_size_t(0)
-            _ffi.call("mp_sort_workspace_bytes", self.M, ctypes.byref(nbytes))
-            ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+            nbytes = _ffi.workspace_bytes("mp_sort_workspace_bytes", self.M)
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             seg_sorted = torch.empty(self.M, dtype=torch.int32, device=dev)
             perm = torch.empty(self.M, dtype=torch.int32, device=dev)
             _ffi.call("mp_sort_segments_i32", _ffi.ptr(seg.contiguous()), self.M, _ffi.ptr(seg_sorted), _ffi.ptr(perm),
-                      _ffi.ptr(ws), nbytes.value, _ffi.stream())
+                      _ffi.ptr(ws), nbytes, _ffi.stream())
             seg = seg_sorted
         _ffi.call("mp_csr_from_sorted_i32", _ffi.ptr(seg.contiguous()) if self.M > 0 else None, self.M, self.N,
                   _ffi.ptr(ptr), _ffi.stream())

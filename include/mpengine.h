@@ -374,32 +374,24 @@ int mp_painn_message_bwd_tiles_f32(const float* s, const float* v, int64_t N, co
                                    const int32_t* tiles, int ntiles, int max_rows, int max_senders, int max_edges,
                                    const float* g_ds, const float* g_dv, float* g_s, float* g_v, float* g_d, float* g_rij,
                                    int accumulate, mpStream_t stream);
-/* PAiNNUpdate.call (painn_conv.py:201-214) around its GEMMs; uv (3N,2F) = v [Wu | Wv] (rows (n,k)):
- * pre:  c (N,2F) = [z | EuclideanNorm_k(v_v)], prod (N,F) = ScalarProduct_k(v_u, v_v);
- * post: z2 = z + prod a_sv + a_ss, v2 = v + a_vv (x) v_u  with a (N,3F) = [a_vv | a_sv | a_ss] (+ PAiNN.py:131-132);
- * post_bwd: g_a (N,3F), g_prod (N,F) from g_z2, g_v2;  pre_bwd: g_z = g_z2 + g_c[:, :F], g_uv (3N,2F). */
-int mp_painn_update_pre_f32(const float* z, const float* uv, int64_t N, float* c, float* prod, mpStream_t stream);
-/* pre + Dense(act) + Dense + post of one PAiNNUpdate in ONE launch (csrc/mp_chain.hip): the element-wise steps as
- * prologue / epilogue of the two-layer chain (W1 (256,128), W2 (128,384) as mp_chain_pack_f32 images).  save_pre keeps
- * c Wd + bd; c_out / prod_out / a_out (any may be NULL) receive what the reverse pass reads. */
+/* PAiNNUpdate.call (painn_conv.py:201-214) after the projection uv (3N,2F) = v [Wu | Wv] (rows (n,k)) in ONE launch
+ * (csrc/mp_chain.hip): the element-wise steps
+ *   pre:  c (N,2F) = [z | EuclideanNorm_k(v_v)], prod (N,F) = ScalarProduct_k(v_u, v_v);
+ *   post: z2 = z + prod a_sv + a_ss, v2 = v + a_vv (x) v_u  with a (N,3F) = [a_vv | a_sv | a_ss] (+ PAiNN.py:131-132)
+ * as prologue / epilogue of the two-layer chain a = Dense(Dense(c, act)) (W1 (256,128), W2 (128,384) as mp_chain_pack_f32
+ * images).  save_pre keeps c Wd + bd; c_out / prod_out / a_out (any may be NULL) receive what the reverse pass reads. */
 int mp_painn_update_fused_f32(const float* z, const float* v, const float* uv, int64_t N, const float* W1_packed,
                               const float* b1, int act1, float alpha1, float* save_pre, const float* W2_packed,
                               const float* b2, float* c_out, float* prod_out, float* a_out, float* z2, float* v2,
                               mpStream_t stream);
-/* ... and its reverse in one launch: post_bwd as the prologue, pre_bwd as the epilogue of the chain against the transposed
+/* ... and its reverse in one launch: g_a (N,3F), g_prod (N,F) from g_z2, g_v2 (reverse of post) as the prologue,
+ * g_z = g_z2 + g_c[:, :F] and g_uv (3N,2F) (reverse of pre) as the epilogue of the chain against the transposed
  * kernels (W1T (384,128) = Wa^T, W2T (128,256) = Wd^T as mp_chain_pack_f32 images; grad_pre = the saved c Wd + bd).
  * g_v2 == NULL: no gradient reaches v'' (the last block of an energy model, whose readout sees z only). */
 int mp_painn_update_fused_bwd_f32(const float* g_z2, const float* g_v2, const float* uv, const float* prod, const float* a,
                                   const float* c, int64_t N, const float* W1T_packed, int act1, float alpha1,
                                   const float* grad_pre, const float* W2T_packed, float* g_z, float* g_uv,
                                   mpStream_t stream);
-int mp_painn_update_post_f32(const float* z, const float* v, const float* uv, const float* prod, const float* a,
-                             int64_t N, float* z2, float* v2, mpStream_t stream);
-int mp_painn_update_post_bwd_f32(const float* g_z2, const float* g_v2, const float* uv, const float* prod,
-                                 const float* a, int64_t N, float* g_a, float* g_prod, mpStream_t stream);
-int mp_painn_update_pre_bwd_f32(const float* g_z2, const float* g_v2, const float* uv, const float* c, const float* a,
-                                const float* g_prod, const float* g_c, int64_t N, float* g_z, float* g_uv,
-                                mpStream_t stream);
 /* Reverse of NodePosition -> EdgeDirectionNormalized / NodeDistanceEuclidean (PAiNN.py:116-118; Schnet.py:116-117 with
  * g_rij = 0): g_xyz[n] = scale * (sum_{recv(e)=n} t_e - sum_{send(e)=n} t_e), t_e = g_d r_ij + (g_rij - (g_rij.r_ij) r_ij)/d,
  * g_d (slices,M) and g_rij (slices,M,3) being partial sums that are added first,

@@ -1,5 +1,5 @@
 """Times the PaiNN message kernels (forward / reverse) of config 3 alone through the C ABI, HIP events on the launch
-stream; MPENGINE_PAINN_VALU=1 selects the VALU builds (A/B)."""
+stream: the gather (VALU) kernels and, where the batch has a tile table, the LDS tile kernel against them."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -66,9 +66,8 @@ if slot.tiles0 is not None:
         slot.tiles0["count"], slot.tiles0["max_rows"], slot.tiles0["max_edges"], timer.time_ms(msg_tiles, 200) * 1e3,
         float((blk["zp"] - ref_z).abs().max()), float(ref_z.abs().max()), float((blk["vp"] - ref_v).abs().max()),
         float(ref_v.abs().max())))
-print("%s: message %.2f us, message reverse %.2f us (N=%d, M=%d, B=%d)" % (
-    "MFMA gather" if os.environ.get("MPENGINE_PAINN_MFMA_GATHER") == "1" else "VALU", timer.time_ms(msg, 200) * 1e3,
-    timer.time_ms(msg_bwd, 200) * 1e3, n, m, B))
+print("VALU: message %.2f us, message reverse %.2f us (N=%d, M=%d, B=%d)" % (
+    timer.time_ms(msg, 200) * 1e3, timer.time_ms(msg_bwd, 200) * 1e3, n, m, B))
 
 # accuracy of the message step against a float64 evaluation of painn_conv.py:99-113 (torch-CPU), per output row
 def f64_reference():
