@@ -147,6 +147,7 @@ _SIGNATURES = {
     "mp_memcpy_h2d_async": [P, P, c_size_t, P],
     "mp_gcn_tile_f32": [P, P],
     "mp_concat_batches": [P, P],
+    "mp_ragged_take": [P, P],
     "mp_acsf_grad_ws_bytes": [c_int64, c_int, P],
     "mp_acsf_g2_f32": [P, P, c_int64, P, c_int64, P, P, P, P, c_int, c_int, c_int, P, P],
     "mp_acsf_g4_f32": [P, P, c_int64, P, c_int64, P, P, P, P, P, c_int, c_int, c_int, c_float, P, P],
@@ -220,6 +221,21 @@ class ConcatDesc(ctypes.Structure):
     """``mp_concat_desc`` of include/mpengine.h (field for field)."""
     _fields_ = [("k", ctypes.c_int32), ("z_is_i64", ctypes.c_int32), ("src", BatchSrc * MP_CONCAT_MAX)] + \
                [(name, c_void_p) for name in ("z", "xyz", "idx", "node_splits", "edge_splits")]
+
+
+MP_TAKE_MAX, MP_TAKE_SCAN_WIDTH = 8, 1024
+
+
+class TakeItem(ctypes.Structure):
+    """``mp_take_item`` of include/mpengine.h."""
+    _fields_ = [("src_values", c_void_p), ("src_splits", c_void_p), ("row_bytes", c_int64),
+                ("dst_values", c_void_p), ("dst_splits", c_void_p), ("dst_rows", c_int64)]
+
+
+class TakeDesc(ctypes.Structure):
+    """``mp_take_desc`` of include/mpengine.h (field for field)."""
+    _fields_ = [("k", ctypes.c_int32), ("reserved", ctypes.c_int32), ("G", c_int64), ("B", c_int64), ("first", c_int64),
+                ("take", c_void_p), ("flags", c_void_p), ("item", TakeItem * MP_TAKE_MAX)]
 
 
 class GcnLayerDesc(ctypes.Structure):

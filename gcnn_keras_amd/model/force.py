@@ -79,7 +79,59 @@ class EnergyForceModel:
             return [o.detach() if torch.is_tensor(o) else o for o in outputs] + [force]
         return eng, force
 
-    predict = __call__
+    # -- the Keras loop over a resident data set (model/loop.py) ------------------------------------------------------------
+    def predict(self, x, batch_size=None, **kwargs):
+        """``batch_size=None``: one call on ``x``.  With an integer the data set ``x`` is served in order, ``batch_size``
+        graphs per call; energies land in one ``(G, states)`` tensor, ragged forces keep the coordinates' splits, padded
+        forces ``(B, Nmax_b, 3)`` land in one zero-filled ``(G, Nmax, 3)``."""
+        if batch_size is None:
+            return self(x, **kwargs)
+        from .loop import predict
+        return predict(self, x, batch_size, kwargs)
+
+    def _batch_losses(self, x, y, sample_weight):
+        """``[total, energy_loss, force_loss]`` of one batch as device scalars: the force pass without ``create_graph``."""
+        from .losses import flat_target
+        sw_energy = self._energy_sample_weight(sample_weight)
+        _, eng, de_dr = self._tape(x, {})
+        f_true = flat_target(y[1], de_dr, x[self.coordinate_input].row_splits_host())
+        loss_e = self._loss_fns[0](eng.detach(), y[0], sw_energy)
+        loss_f = self._loss_fns[1](de_dr.detach(), f_true, None)
+        return [loss_e * self.loss_weights[0] + loss_f * self.loss_weights[1], loss_e, loss_f]
+
+    def evaluate(self, x, y, batch_size=32, sample_weight=None):
+        """``[total, energy_loss, force_loss]`` of the compiled losses over the data set (mean over the batches, weighted
+        by graphs per batch).  ``y = [energy (G, states), force RaggedTensor (G, [N], 3)]``."""
+        from .loop import evaluate
+        self._check_training_call("evaluate", y)
+        return evaluate(self._batch_losses, x, y, batch_size, sample_weight)
+
+    def fit(self, x, y, batch_size=32, epochs=1, shuffle=True, validation_data=None, sample_weight=None, callbacks=None,
+            initial_epoch=0, verbose=0, seed=None):
+        """Keras ``fit`` of the two-output model over a resident data set (see ``Model.fit``); the ``History`` holds
+        ``loss``, ``energy_loss`` and ``force_loss`` (the fork names its outputs ``energy`` and ``force``) and their
+        ``val_`` twins."""
+        from .loop import fit
+        self._check_training_call("fit", y)
+        return fit(self, ["loss", "energy_loss", "force_loss"], x, y, batch_size=batch_size, epochs=epochs,
+                   shuffle=shuffle, validation_data=validation_data, sample_weight=sample_weight, callbacks=callbacks,
+                   initial_epoch=initial_epoch, verbose=verbose, seed=seed)
+
+    def _check_training_call(self, what, y):
+        if getattr(self, "optimizer", None) is None:
+            raise RuntimeError("EnergyForceModel: call compile(optimizer, loss) before %s" % what)
+        if self.esp_input is not None and self.esp_grad_input is not None:
+            raise NotImplementedError("training through the QM/MM esp branch is not implemented")
+        if not isinstance(y, (list, tuple)) or len(y) != 2:
+            raise ValueError("y must be [energy, force]")
+
+    @staticmethod
+    def _energy_sample_weight(sample_weight):
+        if sample_weight is None:
+            return None
+        if not isinstance(sample_weight, (list, tuple)) or len(sample_weight) != 2 or sample_weight[1] is not None:
+            raise NotImplementedError("sample_weight on the force output is not implemented; pass [w_energy, None]")
+        return sample_weight[0]
 
     def _tape(self, inputs, kwargs, create_graph=False):
         """Energy model on the tape, then ``de_dr`` = the flat force values ``(N, 3[, states])`` with the wrapper's sign
@@ -178,17 +230,8 @@ class EnergyForceModel:
         to both outputs) raise ``NotImplementedError``.  The QM/MM ``esp_input`` / ``esp_grad_input`` branch raises
         ``NotImplementedError`` as well."""
         from .losses import flat_target
-        if getattr(self, "optimizer", None) is None:
-            raise RuntimeError("EnergyForceModel: call compile(optimizer, loss) before train_on_batch")
-        if self.esp_input is not None and self.esp_grad_input is not None:
-            raise NotImplementedError("training through the QM/MM esp branch is not implemented")
-        if not isinstance(y, (list, tuple)) or len(y) != 2:
-            raise ValueError("y must be [energy, force]")
-        sw_energy = None
-        if sample_weight is not None:
-            if not isinstance(sample_weight, (list, tuple)) or len(sample_weight) != 2 or sample_weight[1] is not None:
-                raise NotImplementedError("sample_weight on the force output is not implemented; pass [w_energy, None]")
-            sw_energy = sample_weight[0]
+        self._check_training_call("train_on_batch", y)
+        sw_energy = self._energy_sample_weight(sample_weight)
         weights = self.trainable_weights
         saved = [t.requires_grad for t in weights]
         try:

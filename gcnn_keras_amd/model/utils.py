@@ -195,7 +195,36 @@ class Model:
                     return True
         return False
 
-    predict = __call__
+    # -- the Keras loop over a resident data set (model/loop.py) ------------------------------------------------------------
+    def predict(self, x, batch_size=None, **kwargs):
+        """``batch_size=None``: one call on ``x``, ``kwargs`` passed through.  With an integer: ``x`` is the whole data
+        set (device tensors, ``MemoryGraphList.tensor(...)``), served in order ``batch_size`` graphs per model call on the
+        current stream; the results are assembled on the device into what one call over the data set returns."""
+        if batch_size is None:
+            return self(x, **kwargs)
+        from .loop import predict
+        return predict(self, x, batch_size, kwargs)
+
+    def evaluate(self, x, y, batch_size=32, sample_weight=None):
+        """The compiled loss over the data set: mean over the batches, weighted by graphs per batch (Keras)."""
+        import torch
+        from .loop import evaluate
+        if self._loss_fn is None:
+            raise RuntimeError("Model %s: call compile(optimizer, loss) before evaluate" % self.name)
+        with torch.no_grad():
+            return evaluate(lambda xb, yb, swb: self._loss_fn(self(xb), yb, swb), x, y, batch_size, sample_weight)
+
+    def fit(self, x, y, batch_size=32, epochs=1, shuffle=True, validation_data=None, sample_weight=None, callbacks=None,
+            initial_epoch=0, verbose=0, seed=None):
+        """Keras ``fit`` over a resident data set: per epoch the batches of ``data.batching.batch_ids(G, batch_size,
+        shuffle, seed, epoch)``, each cut out on the GPU and given to ``train_on_batch``; returns a ``History``
+        (``loss``, ``val_loss`` with ``validation_data=(x, y[, sample_weight])``, ``lr`` when a callback logs it)."""
+        from .loop import fit
+        if self.optimizer is None:
+            raise RuntimeError("Model %s: call compile(optimizer, loss) before fit" % self.name)
+        return fit(self, ["loss"], x, y, batch_size=batch_size, epochs=epochs, shuffle=shuffle,
+                   validation_data=validation_data, sample_weight=sample_weight, callbacks=callbacks,
+                   initial_epoch=initial_epoch, verbose=verbose, seed=seed)
 
     @property
     def weights(self):

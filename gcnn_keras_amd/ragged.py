@@ -103,6 +103,17 @@ class RaggedTensor:
         s = self.row_splits_host()
         return self.values[int(s[i]):int(s[i + 1])]
 
+    def take(self, ids, ids_device=None, ragged_validate=False):
+        """``tf.gather(self, ids)``: the rows of graphs ``ids[0], ids[1], ...`` back to back with rebased row splits, as a
+        fresh tensor (``mp_ragged_take``; ``gcnn_keras_amd.data.batching.take_batch`` is the form for several tensors).
+        ``ids``: host integers; ``ids_device``: their device int64 copy when the caller holds one (uploaded otherwise)."""
+        from .data.batching import take_batch
+        _ffi.require_device(self.values, self.row_splits)
+        ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+        if ids_device is None:
+            ids_device = torch.from_numpy(ids).to(self.values.device)
+        return take_batch([self], ids_device, ids, ragged_validate=ragged_validate)[0]
+
     def numpy_rows(self):
         s = self.row_splits_host()
         v = self.values.cpu().numpy()

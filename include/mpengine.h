@@ -543,6 +543,29 @@ typedef struct mp_concat_desc {
 } mp_concat_desc;
 int mp_concat_batches(const mp_concat_desc* desc_host, mpStream_t stream);
 
+/* ---------------------------------------------------------------- batches of a resident data set ------------ */
+/* tf.gather(ragged, ids) for up to MP_TAKE_MAX ragged tensors that share their graph axis (G graphs), in one call and
+ * without a host read-back: item i receives the rebased dst_splits (B + 1 entries) and the rows of graphs take[0],
+ * take[1], ... back to back (bit-exact copy; per-graph edge indices are sample indices, kgcnn/layers/base.py:27, and stay
+ * as they are).  take == NULL means the contiguous range first .. first + B - 1.  row_bytes is a multiple of 4; dst_rows
+ * is the number of rows dst_values holds (the host knows it from its copy of the splits) and nothing is written past it.
+ * An id outside [0, G) is clamped and MP_FLAG_OOB is ORed into *flags.  The scan behind dst_splits walks B in passes of
+ * MP_TAKE_SCAN_WIDTH entries; any B is correct.  B == 0 returns MP_OK without a launch. */
+#define MP_TAKE_MAX 8
+#define MP_TAKE_SCAN_WIDTH 1024
+typedef struct mp_take_item {
+  const void* src_values; const int64_t* src_splits; int64_t row_bytes;
+  void* dst_values; int64_t* dst_splits; int64_t dst_rows;
+} mp_take_item;
+typedef struct mp_take_desc {
+  int32_t k, reserved;
+  int64_t G, B, first;
+  const int64_t* take;
+  int32_t* flags;
+  mp_take_item item[MP_TAKE_MAX];
+} mp_take_desc;
+int mp_ragged_take(const mp_take_desc* desc_host, mpStream_t stream);
+
 /* ---------------------------------------------------------------- fused GCN forward -------------------------- */
 /* The forward of kgcnn.literature.GCN.make_model (kgcnn/literature/GCN.py:95-109) in 1 + depth launches on 16-node
  * tiles, each launch = one producer of the tile followed by up to three Keras Dense layers on it:
