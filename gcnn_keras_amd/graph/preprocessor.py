@@ -1,9 +1,14 @@
-"""On-GPU ``SetRange`` (mirror of kgcnn/graph/preprocessor.py:255-314 for a ragged batch resident in HBM).
+"""On-GPU ``SetRange`` and ``SetAngle`` (mirrors of kgcnn/graph/preprocessor.py:255-368 for a ragged batch resident in
+HBM).
 
 The reference runs ``define_adjacency_from_distance`` (kgcnn/graph/adj.py:537-593) per molecule in NumPy on the host
 and re-uploads the edge lists; here the whole batch goes through two kernels around one prefix sum
 (csrc/mp_radius.hip).  Same rule: ``dist < max_distance`` AND among the ``max_neighbours + 1`` nearest entries of the
 row (exclusive mode), no self loops, row-major ``(i, j)`` order - hence receiver-sorted output.
+
+``SetAngle`` is the second half of the geometry pre-step: the reference loops over the edges of one molecule in Python
+(``get_angle_indices``, kgcnn/graph/adj.py:300-385); here the angle list of the whole batch comes from a count and a
+fill kernel around one prefix sum (csrc/mp_angle.hip), walking the CSR buckets the edge list's index plan already has.
 """
 import torch
 
@@ -85,3 +90,116 @@ class SetRange:
         from ..ragged import IndexPlan
         indices.attach_plan(node_coordinates, IndexPlan.from_prepared(indices, node_coordinates, cols, node_ptr))
         return indices, RaggedTensor(dist, edge_splits)
+
+
+class SetAngle:
+    """Angle triples ``(i, j, k)``, edge pairs ``(n, m)`` and angle values of a ragged batch of edge lists, built on the
+    device (``mp_angle_list_*``).  Keywords and defaults of the reference's ``SetAngle``
+    (kgcnn/graph/preprocessor.py:337-342).  The order is by ``n``, then ``m`` ascending - what ``check_sorted=True``
+    yields, so ``check_sorted`` changes nothing here.  ``allow_self_edges=True`` is not implemented."""
+
+    def __init__(self, *, range_indices: str = "range_indices", node_coordinates: str = "node_coordinates",
+                 angle_indices: str = "angle_indices", angle_indices_nodes: str = "angle_indices_nodes",
+                 angle_attributes: str = "angle_attributes", allow_multi_edges: bool = False,
+                 allow_self_edges: bool = False, allow_reverse_edges: bool = False, edge_pairing: str = "kj",
+                 check_sorted: bool = True, compute_angles: bool = True, name="set_angle", **kwargs):
+        if allow_self_edges:
+            raise NotImplementedError("on-GPU SetAngle does not pair an edge with itself (allow_self_edges=True)")
+        if "k" not in edge_pairing:
+            raise ValueError("Edge pairing must have index 'k'.")
+        if "i" not in edge_pairing and "j" not in edge_pairing:
+            raise ValueError("Edge pairing must have at least one fix index 'i' or 'j'.")
+        self.name = name
+        self._config_kwargs = {"node_coordinates": node_coordinates, "range_indices": range_indices,
+                               "angle_indices": angle_indices, "angle_indices_nodes": angle_indices_nodes,
+                               "angle_attributes": angle_attributes, "allow_multi_edges": allow_multi_edges,
+                               "compute_angles": compute_angles, "allow_self_edges": allow_self_edges,
+                               "edge_pairing": edge_pairing, "allow_reverse_edges": allow_reverse_edges,
+                               "check_sorted": check_sorted}
+        self.allow_multi_edges, self.allow_reverse_edges = bool(allow_multi_edges), bool(allow_reverse_edges)
+        self.compute_angles = bool(compute_angles)
+        self.pos_k = 0 if edge_pairing[0] == "k" else 1       # kgcnn/graph/adj.py:335-337
+        self.pos_fix = 1 - self.pos_k
+        self.pos_ij = 0 if "i" in edge_pairing else 1
+
+    def get_config(self):
+        return {"name": self.name, **self._config_kwargs}
+
+    @property
+    def produces(self):
+        """Property names this preprocessor adds when used on a dict of packed tensors (MD driver)."""
+        names = (self._config_kwargs["angle_indices"], self._config_kwargs["angle_indices_nodes"])
+        return names + ((self._config_kwargs["angle_attributes"],) if self.compute_angles else ())
+
+    def __call__(self, range_indices, node_coordinates=None):
+        if isinstance(range_indices, dict):  # dict of packed device tensors -> dict of the new properties
+            out = self._run(range_indices[self._config_kwargs["range_indices"]],
+                            range_indices[self._config_kwargs["node_coordinates"]])
+            return {name: t for name, t in zip(self.produces, out)}
+        return self._run(range_indices, node_coordinates)
+
+    def _count(self, range_indices, eplan):
+        """Pass 1: ``(off (M+1) int64, angle_splits (G+1) int64, A)`` of the edge list with index plan ``eplan``."""
+        m, g, dev = eplan.M, eplan.G, eplan.cols.device
+        off = torch.zeros(m + 1, dtype=torch.int64, device=dev)
+        angle_splits = torch.zeros(g + 1, dtype=torch.int64, device=dev)
+        if m == 0 or g == 0:
+            return off, angle_splits, 0
+        ptr, perm, _ = eplan.csr(self.pos_fix)
+        nbytes = _ffi.workspace_bytes("mp_angle_list_workspace_bytes", m)
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        _ffi.call("mp_angle_list_count_i32", _ffi.ptr(eplan.cols), m, eplan.N, _ffi.ptr(ptr), _ffi.ptr(perm),
+                  _ffi.ptr(range_indices.row_splits), g, self.pos_fix, self.pos_ij, int(self.allow_multi_edges),
+                  int(self.allow_reverse_edges), _ffi.ptr(off), _ffi.ptr(angle_splits), _ffi.ptr(ws), nbytes,
+                  _ffi.stream())
+        return off, angle_splits, int(off[-1].item())  # data-dependent output size: one host read, as in SetRange
+
+    def _fill(self, range_indices, node_coordinates, eplan, off, a):
+        """Pass 2: ``(triples (A,3), pairs (A,2), triple columns (3,A), pair columns (2,A), theta (A,1) or None,
+        triple CSR (N+1) or None, pair CSR (M+1))`` for the ``off`` and ``A`` of :meth:`_count`."""
+        m, n, dev = eplan.M, eplan.N, eplan.cols.device
+        xyz = node_coordinates.values.contiguous()
+        ptr, perm, _ = eplan.csr(self.pos_fix)
+        sorted0 = eplan.is_sorted(0)
+        triples = torch.empty((a, 3), dtype=torch.int64, device=dev)
+        pairs = torch.empty((a, 2), dtype=torch.int64, device=dev)
+        tcols = torch.empty((3, max(a, 1)), dtype=torch.int32, device=dev)
+        pcols = torch.empty((2, max(a, 1)), dtype=torch.int32, device=dev)
+        theta = torch.empty((a, 1), dtype=torch.float32, device=dev) if self.compute_angles else None
+        tptr = torch.zeros(n + 1, dtype=torch.int32, device=dev) if sorted0 else None
+        pptr = torch.zeros(m + 1, dtype=torch.int32, device=dev)
+        eptr0 = eplan.csr(0)[0] if sorted0 else None
+        _ffi.call("mp_angle_list_fill_f32", _ffi.ptr(eplan.cols), m, n, _ffi.ptr(ptr), _ffi.ptr(perm),
+                  _ffi.ptr(node_coordinates.row_splits), _ffi.ptr(range_indices.row_splits), eplan.G, self.pos_fix,
+                  self.pos_ij, self.pos_k, int(self.allow_multi_edges), int(self.allow_reverse_edges), _ffi.ptr(off), a,
+                  _ffi.ptr(xyz), _ffi.ptr(triples), _ffi.ptr(pairs), _ffi.ptr(tcols), _ffi.ptr(pcols), _ffi.ptr(theta),
+                  _ffi.ptr(eptr0), _ffi.ptr(tptr), _ffi.ptr(pptr), _ffi.stream())
+        return triples, pairs, tcols, pcols, theta, tptr, pptr
+
+    def _run(self, range_indices: RaggedTensor, node_coordinates: RaggedTensor):
+        """``range_indices``: ragged ``(batch, [M], 2)`` int64; ``node_coordinates``: ragged ``(batch, [N], 3)`` float32.
+        Returns ``(angle_indices, angle_indices_nodes, angle_attributes)``: ragged ``(batch, [A], 2)`` int64 edge pairs,
+        ``(batch, [A], 3)`` int64 node triples and ``(batch, [A], 1)`` float32 angles (``None`` without
+        ``compute_angles``).  Both index tensors carry a ready index plan: the triples against the coordinates'
+        partition, the pairs against ``range_indices``' partition."""
+        from ..ragged import IndexPlan
+        _ffi.require_device(node_coordinates.values, range_indices.values, range_indices.row_splits,
+                            node_coordinates.row_splits)
+        if self.compute_angles and node_coordinates.values.dtype != torch.float32:
+            raise TypeError("SetAngle expects float32 coordinates, got %s" % node_coordinates.values.dtype)
+        eplan = range_indices.index_plan(node_coordinates)
+        if eplan.K != 2:
+            raise ValueError("SetAngle expects range indices of shape (batch, [M], 2)")
+        off, angle_splits, a = self._count(range_indices, eplan)
+        triples, pairs, tcols, pcols, theta, tptr, pptr = self._fill(range_indices, node_coordinates, eplan, off, a)
+        angle_nodes = RaggedTensor(triples, angle_splits)
+        angle_edges = RaggedTensor(pairs, angle_splits)
+        # column 0 of the triples is the receiver column of the edge list, edge by edge: sorted where that one is;
+        # column 0 of the pairs is the edge index itself: always sorted.  Column 1 is not claimed.
+        oob = eplan.flags_host() & _ffi.MP_FLAG_OOB
+        tflags = oob | _ffi.MP_FLAG_UNSORTED_COL1 | (0 if eplan.is_sorted(0) else _ffi.MP_FLAG_UNSORTED_COL0)
+        angle_nodes.attach_plan(node_coordinates,
+                                IndexPlan.from_prepared(angle_nodes, node_coordinates, tcols, tptr, flags=tflags))
+        angle_edges.attach_plan(range_indices, IndexPlan.from_prepared(angle_edges, range_indices, pcols, pptr,
+                                                                       flags=oob | _ffi.MP_FLAG_UNSORTED_COL1))
+        return angle_edges, angle_nodes, (RaggedTensor(theta, angle_splits) if self.compute_angles else None)

@@ -170,17 +170,23 @@ class IndexPlan:
         self._csr = {}
 
     @classmethod
-    def from_prepared(cls, idx, nodes, cols, csr_ptr=None):
+    def from_prepared(cls, idx, nodes, cols, csr_ptr=None, flags=None):
         """Plan for indices whose shifted int32 columns (and receiver CSR) a producer kernel already wrote
-        (on-GPU ``SetRange``): range-checked and receiver-sorted by construction, nothing to launch."""
+        (on-GPU ``SetRange`` / ``SetAngle``): nothing to launch.  ``flags``: the ``MP_FLAG_*`` word the producer knows to
+        hold; by default range-checked, column 0 sorted and column 1 not claimed (``SetRange``'s receiver-sorted list).
+        ``csr_ptr`` (the CSR offsets over column 0) is used only where column 0 is sorted."""
         self = cls.__new__(cls)
         self.M, self.K = int(idx.values.shape[0]), int(idx.values.shape[1])
         self.N, self.G = int(nodes.values.shape[0]), idx.nrows()
         self.cols = cols
-        self.flags = torch.zeros(1, dtype=torch.int32, device=cols.device)
-        self._flags_host = _ffi.MP_FLAG_UNSORTED_COL1  # column 0 sorted; column 1 not claimed
+        if flags is None:
+            self.flags = torch.zeros(1, dtype=torch.int32, device=cols.device)
+            self._flags_host = _ffi.MP_FLAG_UNSORTED_COL1  # column 0 sorted; column 1 not claimed
+        else:
+            self.flags = torch.full((1,), int(flags), dtype=torch.int32, device=cols.device)
+            self._flags_host = int(flags)
         self._csr = {}
-        if csr_ptr is not None:
+        if csr_ptr is not None and not (self._flags_host & _ffi.MP_FLAG_UNSORTED_COL0):
             self._csr[(0, False)] = self._csr[(0, True)] = (csr_ptr, None, cols[0, :self.M])
         return self
 

@@ -458,6 +458,33 @@ int mp_radius_graph_fill_f32(const float* xyz, const int64_t* node_splits, int64
                              int max_neighbours, const int32_t* node_ptr, int64_t M, int64_t* idx_out, int32_t* recv,
                              int32_t* send, float* dist, mpStream_t stream);
 
+/* ---------------------------------------------------------------- on-GPU SetAngle ------------------------ */
+/* SetAngle.call, kgcnn/graph/preprocessor.py:354-368 via get_angle_indices / get_angle (kgcnn/graph/adj.py:300-415),
+ * allow_self_edges=False, for a whole ragged batch of edge lists.  edge_cols (2,M): the shifted, clamped int32 columns
+ * of the edge list's index plan; ptr (N+1) / perm (M, or NULL when the column is sorted): the plan's CSR over column
+ * pos_fix.  pos_k is the position of k in edge_pairing, pos_fix the other one, pos_ij = 0 if the pairing names i,
+ * else 1.  Partners of edge n = (i, j): the edges m != n with idx[m, pos_fix] == idx[n, pos_ij], without those equal to
+ * (i, j) / (j, i) unless allow_multi_edges / allow_reverse_edges.  Order: by n, then m ascending.
+ * Pass 1 counts the partners of every edge and scans them in int64: off (M+1) = first output row of every edge,
+ * angle_splits (G+1) int64; the caller reads A = off[M] to size the outputs.  Pass 2 writes, each pointer nullable:
+ * triples (A,3) int64 node ids (i, j, k) local to the graph, pairs (A,2) int64 edge ids (n, m) local to the graph's
+ * edge list, triple_cols (3,A) / pair_cols (2,A) int32 shifted ids (the index-plan columns of the triples against the
+ * node partition and of the pairs against the edge partition), theta (A) = atan2(|v1 x v2|, v1 . v2) with
+ * v1 = x_i - x_j, v2 = x_j - x_k, and the column-0 CSRs triple_ptr (N+1; needs edge_ptr0, the edge list's column-0
+ * CSR, and is meaningful when that column is sorted) and pair_ptr (M+1).  A >= 2^31 is MP_EINVAL.  M == 0 or G == 0
+ * returns MP_OK without touching the device. */
+int mp_angle_list_workspace_bytes(int64_t M, size_t* bytes_out_host);
+int mp_angle_list_count_i32(const int32_t* edge_cols, int64_t M, int64_t N, const int32_t* ptr, const int32_t* perm,
+                            const int64_t* edge_splits, int64_t G, int pos_fix, int pos_ij, int allow_multi_edges,
+                            int allow_reverse_edges, int64_t* off, int64_t* angle_splits, void* ws, size_t ws_bytes,
+                            mpStream_t stream);
+int mp_angle_list_fill_f32(const int32_t* edge_cols, int64_t M, int64_t N, const int32_t* ptr, const int32_t* perm,
+                           const int64_t* node_splits, const int64_t* edge_splits, int64_t G, int pos_fix, int pos_ij,
+                           int pos_k, int allow_multi_edges, int allow_reverse_edges, const int64_t* off, int64_t A,
+                           const float* xyz, int64_t* triples, int64_t* pairs, int32_t* triple_cols,
+                           int32_t* pair_cols, float* theta, const int32_t* edge_ptr0, int32_t* triple_ptr,
+                           int32_t* pair_ptr, mpStream_t stream);
+
 /* ---------------------------------------------------------------- backward helpers (forces) -------------- */
 /* EnergyForceModel, kgcnn/model/force.py:159-186: F = -dE/dx needs one reverse pass.  Gather-backward is
  * mp_segment_reduce_csr_f32 over the CSR of the gathered column, segment-sum-backward is mp_gather_rows_f32 by the
