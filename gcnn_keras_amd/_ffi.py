@@ -112,6 +112,9 @@ _SIGNATURES = {
     "mp_schnet_node_in_f32": [P, c_int64, P, c_int, c_int, P, P, P, P, P, c_int, P],
     "mp_schnet_stage0_f32": [P, c_int64, P, c_int, c_int, P, P, P, P, P, P, c_int64, P, P, c_int64, P, P, P, P, P, c_int,
                              P],
+    "mp_schnet_embed_table_f32": [P, c_int, c_int, P, P, P, P, P, P, c_int, P],
+    "mp_schnet_node_in_table_f32": [P, c_int64, c_int, P, P, P, P, c_int, P],
+    "mp_schnet_stage0_table_f32": [P, c_int64, c_int, P, P, P, P, P, c_int64, P, P, c_int64, P, P, P, P, P, c_int, P],
     "mp_schnet_node_update_f32": [P, c_int64, P, P, P, P, P, P, P, c_int, P],
     "mp_schnet_node_last_f32": [P, c_int64, P, P, P, P, P, P, P, P, P, P, c_int, P],
     "mp_schnet_readout_f32": [P, P, c_int64, P, P, P, P, P, P],
@@ -187,6 +190,7 @@ _SIGNATURES = {
 _RESTYPES = {"mp_last_error": c_char_p}
 
 MP_SCHNET_MAX_DEPTH = 8
+MP_SCHNET_TABLE_MAX_ROWS = 2048   # include/mpengine.h: rows of the node-input tables (vocab + 1)
 
 
 class SchnetForwardDesc(ctypes.Structure):
@@ -199,7 +203,8 @@ class SchnetForwardDesc(ctypes.Structure):
                                                  "W0", "b0")]
                 + [(name, c_void_p * MP_SCHNET_MAX_DEPTH) for name in ("Wx", "packed", "W2", "b2", "W3", "b3")]
                 + [(name, c_void_p) for name in ("Wl0", "bl0", "Wl1", "bl1", "Wo0", "bo0", "Wo1", "bo1", "recv", "send",
-                                                 "dist", "flags_word", "n", "x", "agg", "h", "out")])
+                                                 "dist", "flags_word", "n", "x", "agg", "h", "out",
+                                                 "n_table", "x_table")])
 
 
 class SchnetForceDesc(ctypes.Structure):

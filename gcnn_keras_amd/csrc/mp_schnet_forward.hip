@@ -1,4 +1,4 @@
-// Whole fused SchNet forward behind ONE C-ABI call: the eight launches of csrc/mp_schnet_node.hip / mp_cfconv.hip in
+// Whole fused SchNet forward behind ONE C-ABI call: the eight launches of csrc/mp_schnet_table.hip / mp_schnet_node.hip / mp_cfconv.hip in
 // sequence on the caller's stream, from a descriptor that holds every pointer and size of a bound batch slot.
 //
 // Why next to the HIP-graph replay: a captured graph is bound to one batch's buffers and sizes, and capturing costs
@@ -14,9 +14,16 @@ int mp_schnet_forward_launch(const mp_schnet_forward_desc* d, mpStream_t stream)
   MP_REQUIRE(d != nullptr, "mp_schnet_forward_launch: null descriptor");
   MP_REQUIRE(d->depth >= 1 && d->depth <= MP_SCHNET_MAX_DEPTH, "mp_schnet_forward_launch: depth %d not in 1..%d",
              d->depth, MP_SCHNET_MAX_DEPTH);
-  int rc = mp_schnet_stage0_f32(d->numbers, d->N, d->embedding, d->vocab, d->emb_dim == 128 ? 128 : 64, d->W0, d->b0,
-                                d->Wx[0], d->n, d->x, d->idx, d->M, d->node_splits, d->edge_splits, d->G, d->xyz,
-                                d->recv, d->send, d->dist, d->flags_word, d->flags & (3 | 64 | 256 | 512), stream);
+  int rc;
+  if (d->n_table && d->x_table) {   // the node-input chain as a row gather (mp_schnet_embed_table_f32)
+    rc = mp_schnet_stage0_table_f32(d->numbers, d->N, d->vocab, d->n_table, d->x_table, d->n, d->x, d->idx, d->M,
+                                    d->node_splits, d->edge_splits, d->G, d->xyz, d->recv, d->send, d->dist,
+                                    d->flags_word, d->flags & 256, stream);
+  } else {
+    rc = mp_schnet_stage0_f32(d->numbers, d->N, d->embedding, d->vocab, d->emb_dim == 128 ? 128 : 64, d->W0, d->b0,
+                              d->Wx[0], d->n, d->x, d->idx, d->M, d->node_splits, d->edge_splits, d->G, d->xyz,
+                              d->recv, d->send, d->dist, d->flags_word, d->flags & (3 | 64 | 256 | 512), stream);
+  }
   if (rc != MP_OK) return rc;
   for (int i = 0; i < d->depth; ++i) {
     rc = mp_cfconv_gauss_fused_f32(d->x, d->N, d->dist, d->bins, d->g_distance, d->g_sigma, d->g_offset, d->packed[i],

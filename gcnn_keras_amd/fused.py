@@ -1,7 +1,8 @@
 """Fused SchNet forward: the arithmetic of kgcnn/literature/Schnet.py:104-148 in eight kernels, replayed from a HIP graph.
 
     stage0              edge_prepare (index shift, receiver/sender split, flags, distance) and node_in
-                        (Embedding -> Dense(64->128) -> Dense_nobias) on disjoint workgroups             (1 launch)
+                        (Embedding -> Dense(64->128) -> Dense_nobias: rows of the per-number tables
+                        that pack_weights builds with the chain) on disjoint workgroups                  (1 launch)
     per block:          cfconv_gauss_fused (Gauss basis, filter MLP, gather, multiply, segment-sum)     (depth launches)
                         node_update / node_last (2-3 chained Dense on the node tile, residual)         (depth launches)
     readout             PoolingNodes(sum) + output MLP                                                 (1 launch)
@@ -82,16 +83,25 @@ def node_weight_names(depth):
 
 def pack_weights(p, depth, bins, out=None):
     """Kernel-side images of the weights: ``mp_cfconv_pack_f32`` (filter MLP of every interaction block in the cfconv
-    kernel's LDS order) and ``mp_schnet_node_pack_f32`` (node-side matrices in register-slice order).  Packed once per
-    weight update; ``out`` re-fills existing images in place (captured graphs keep pointing at them)."""
+    kernel's LDS order), ``mp_schnet_node_pack_f32`` (node-side matrices in register-slice order) and the node-input
+    tables (``mp_schnet_embed_table_f32``: the rows the input chain writes for every node number of the vocabulary, one
+    pair of tables per node build).  Packed once per weight update; ``out`` re-fills existing images in place (captured
+    graphs keep pointing at them)."""
     nfl = _ffi.lib().mp_cfconv_packed_floats()
+    rows = int(p["embedding"].shape[0]) + 1
     if out is None:
         out = {"cfconv": [torch.empty(nfl, dtype=torch.float32, device="cuda") for _ in range(depth)],
                "node": {k: torch.empty(p[k].numel(), dtype=torch.float32, device="cuda")
                         for k in node_weight_names(depth)},
                # the same matrices as three bf16 pieces per element (the forward's node kernels on the bf16 pipe)
                "node_bf": {k: torch.empty(p[k].numel() * 3 // 2, dtype=torch.float32, device="cuda")
-                           for k in node_weight_names(depth)}}
+                           for k in node_weight_names(depth)},
+               # (2, vocab + 1, 128): n and x of the input chain per node number, built from the FP32 ("node") and from
+               # the bf16-piece ("node_bf") images; "ws": the chain's input numbers.  Large vocabularies keep the chain.
+               "table": None if rows > _ffi.MP_SCHNET_TABLE_MAX_ROWS else
+               {"node": torch.empty((2, rows, 128), dtype=torch.float32, device="cuda"),
+                "node_bf": torch.empty((2, rows, 128), dtype=torch.float32, device="cuda"),
+                "ws": torch.empty(rows, dtype=torch.float32, device="cuda")}}
     for i in range(depth):
         pre = "interaction%d/cfconv/" % i
         _ffi.call("mp_cfconv_pack_f32", _ffi.ptr(p[pre + "dense1/kernel"]), _ffi.ptr(p.get(pre + "dense1/bias")),
@@ -103,6 +113,14 @@ def pack_weights(p, depth, bins, out=None):
     for k, image in out.get("node_bf", {}).items():
         _ffi.call("mp_schnet_node_pack_bf16_f32", _ffi.ptr(p[k]), int(p[k].shape[0]), int(p[k].shape[1]),
                   _ffi.ptr(image), _ffi.stream())
+    if out.get("table") is not None:
+        emb = p["embedding"]
+        for kind, flags in (("node", 2), ("node_bf", 2 | 64)):
+            w, t = out[kind], out["table"][kind]
+            _ffi.call("mp_schnet_embed_table_f32", _ffi.ptr(emb), int(emb.shape[0]), int(emb.shape[1]),
+                      _ffi.ptr(w["dense0/kernel"]), _ffi.ptr(p.get("dense0/bias")),
+                      _ffi.ptr(w["interaction0/dense1/kernel"]), _ffi.ptr(out["table"]["ws"]), _ffi.ptr(t[0]),
+                      _ffi.ptr(t[1]), flags, _ffi.stream())
     torch.cuda.current_stream().synchronize()
     return out
 
@@ -228,6 +246,12 @@ class FusedSchnet:
         if "node_bf" in images and os.environ.get("MPENGINE_NODE_BF16", "1") != "0":
             self.node_images = images["node_bf"]
             self.flags_arg |= 64
+        # stage 0's node role as a row gather from the input tables of the build chosen above; MPENGINE_NODE_TABLE=0 keeps
+        # the chain.  MPENGINE_STAGE0_EDGE_CAP: cap of stage 0's edge workgroups (multiple of 16), for A/B runs.
+        self.table = None
+        if images.get("table") is not None and os.environ.get("MPENGINE_NODE_TABLE", "1") != "0":
+            self.table = images["table"]["node_bf" if self.flags_arg & 64 else "node"]
+        self._edge_cap = (int(os.environ.get("MPENGINE_STAGE0_EDGE_CAP", "0")) // 16 & 255) << 16
         self._own_stream = None     # made on first use (capture / engine.SchnetForward): a slot that is bound, launched
         self.graph = None           # once and dropped never needs one
         self._ring = None
@@ -319,7 +343,15 @@ class FusedSchnet:
         p, b, w = self.p, self._b, self.node_images
         if self._pre is not None:
             self._pre()
-        if self.sorted or self.M == 0:
+        t = self.table
+        if (self.sorted or self.M == 0) and t is not None:
+            # stage 0: node-input rows gathered from the tables and edge preparation in one launch
+            _ffi.call("mp_schnet_stage0_table_f32", _ffi.ptr(b["z"]), self.N, int(p["embedding"].shape[0]),
+                      _ffi.ptr(t[0]), _ffi.ptr(t[1]), _ffi.ptr(self.n), _ffi.ptr(self.x), _ffi.ptr(b["idx"]), self.M,
+                      _ffi.ptr(b["ns"]), _ffi.ptr(b["es"]), self.G, _ffi.ptr(b["xyz"]), _ffi.ptr(self.recv),
+                      _ffi.ptr(self.send), _ffi.ptr(self.dist), _ffi.ptr(self.flags), self.node_flags | self._edge_cap,
+                      _ffi.stream())
+        elif self.sorted or self.M == 0:
             # stage 0: node-input chain and edge preparation in one launch (independent work on disjoint workgroups)
             _ffi.call("mp_schnet_stage0_f32", _ffi.ptr(b["z"]), self.N, _ffi.ptr(p["embedding"]),
                       int(p["embedding"].shape[0]), self.emb_dim, _ffi.ptr(w["dense0/kernel"]), _ffi.ptr(p.get("dense0/bias")),
@@ -331,10 +363,15 @@ class FusedSchnet:
             self._prepare()
             _ffi.call("mp_sort_segments_i32", _ffi.ptr(self.recv), self.M, _ffi.ptr(self.recv_sorted),
                       _ffi.ptr(self.perm), _ffi.ptr(self.sort_ws), self.sort_ws_bytes, _ffi.stream())
-            _ffi.call("mp_schnet_node_in_f32", _ffi.ptr(b["z"]), self.N, _ffi.ptr(p["embedding"]),
-                      int(p["embedding"].shape[0]), self.emb_dim, _ffi.ptr(w["dense0/kernel"]), _ffi.ptr(p.get("dense0/bias")),
-                      _ffi.ptr(w["interaction0/dense1/kernel"]), _ffi.ptr(self.n), _ffi.ptr(self.x),
-                      self.node_flags, _ffi.stream())
+            if t is not None:
+                _ffi.call("mp_schnet_node_in_table_f32", _ffi.ptr(b["z"]), self.N, int(p["embedding"].shape[0]),
+                          _ffi.ptr(t[0]), _ffi.ptr(t[1]), _ffi.ptr(self.n), _ffi.ptr(self.x), self.node_flags,
+                          _ffi.stream())
+            else:
+                _ffi.call("mp_schnet_node_in_f32", _ffi.ptr(b["z"]), self.N, _ffi.ptr(p["embedding"]),
+                          int(p["embedding"].shape[0]), self.emb_dim, _ffi.ptr(w["dense0/kernel"]),
+                          _ffi.ptr(p.get("dense0/bias")), _ffi.ptr(w["interaction0/dense1/kernel"]), _ffi.ptr(self.n),
+                          _ffi.ptr(self.x), self.node_flags, _ffi.stream())
         for i in range(self.depth):
             pre = "interaction%d/" % i
             self._cfconv(i, self.agg)
@@ -506,6 +543,7 @@ class FusedSchnet:
             d.numbers, d.xyz, d.idx = addr(b["z"]), addr(b["xyz"]), addr(b["idx"])
             d.node_splits, d.edge_splits = addr(b["ns"]), addr(b["es"])
             d.out = addr(self.out)
+            self._descriptor_tables(d)
             return d
         d = _ffi.SchnetForwardDesc()
         if ws is not None:
@@ -529,7 +567,12 @@ class FusedSchnet:
         d.emb_dim = self.emb_dim
         d.recv, d.send, d.dist, d.flags_word = addr(self.recv), addr(self.send), addr(self.dist), addr(self.flags)
         d.n, d.x, d.agg, d.h, d.out = addr(self.n), addr(self.x), addr(self.agg), addr(self.h), addr(self.out)
+        self._descriptor_tables(d)
         return d
+
+    def _descriptor_tables(self, d):
+        t = self.table
+        d.n_table, d.x_table = (None, None) if t is None else (t[0].data_ptr(), t[1].data_ptr())
 
     def launch_direct(self):
         """The same eight launches as the captured graph, issued directly by ONE C-ABI call on this slot's stream

@@ -434,6 +434,27 @@ int mp_schnet_stage0_f32(const float* numbers, int64_t N, const float* emb, int 
                          const float* b0, const float* Wx, float* n_out, float* x_out, const int64_t* idx, int64_t M,
                          const int64_t* node_splits, const int64_t* edge_splits, int64_t G, const float* xyz,
                          int32_t* recv, int32_t* send, float* dist, int32_t* flags, int flags_arg, mpStream_t stream);
+/* The node-input chain as a table: n and x of mp_schnet_node_in_f32 are functions of the node number alone, so the chain
+ * runs once per weight update on the numbers 0 .. vocab-1, -1 (same build: flags bits 0, 1, 6 as the forward uses them)
+ * and fills n_table / x_table, (vocab + 1, 128) each: row r < vocab = the chain's rows for a node with number r, row
+ * vocab = its rows for a number outside 0 .. vocab-1 (zero embedding row: b0 resp. b0 Wx).  Bit-identical to the chain by
+ * construction.  numbers_ws: (vocab + 1) floats of scratch.  vocab + 1 <= MP_SCHNET_TABLE_MAX_ROWS (both tables: 2 MB, half
+ * of one XCD's L2); larger vocabularies keep the chain. */
+#define MP_SCHNET_TABLE_MAX_ROWS 2048
+int mp_schnet_embed_table_f32(const float* emb, int vocab, int emb_dim, const float* W0, const float* b0,
+                              const float* Wx, float* numbers_ws, float* n_table, float* x_table, int flags,
+                              mpStream_t stream);
+/* mp_schnet_node_in_f32 / mp_schnet_stage0_f32 with the chain replaced by a row gather from the tables: per node the number
+ * is read (float32, or int64 with flags bit 8; cast and range rule of the chain) and row r of n_table / x_table is copied
+ * to n_out / x_out.  No LDS, no barrier, 256-thread workgroups.  The stage-0 form runs the edge preparation on further
+ * workgroups of the same launch (at most 128; flags_arg bits 16-23, if set: the cap in units of 16 workgroups, for A/B
+ * runs) and falls back to two launches for large batches as mp_schnet_stage0_f32 does. */
+int mp_schnet_node_in_table_f32(const float* numbers, int64_t N, int vocab, const float* n_table, const float* x_table,
+                                float* n_out, float* x_out, int flags, mpStream_t stream);
+int mp_schnet_stage0_table_f32(const float* numbers, int64_t N, int vocab, const float* n_table, const float* x_table,
+                               float* n_out, float* x_out, const int64_t* idx, int64_t M, const int64_t* node_splits,
+                               const int64_t* edge_splits, int64_t G, const float* xyz, int32_t* recv, int32_t* send,
+                               float* dist, int32_t* flags, int flags_arg, mpStream_t stream);
 int mp_schnet_node_update_f32(float* agg, int64_t N, const float* W2, const float* b2, const float* W3,
                               const float* b3, float* n_inout, const float* Wx_next, float* x_out, int flags,
                               mpStream_t stream);
@@ -549,6 +570,7 @@ typedef struct mp_schnet_forward_desc {
   const float* Wo0; const float* bo0; const float* Wo1; const float* bo1;   /* output_mlp; Wo0 == NULL: linear head Wo1 */
   int32_t* recv; int32_t* send; float* dist; int32_t* flags_word;           /* (M) work buffers, flag word */
   float* n; float* x; float* agg; float* h; float* out;                     /* (N,128) x3 [agg zeroed], (N,64), (G,1) */
+  const float* n_table; const float* x_table;   /* mp_schnet_embed_table_f32 tables; NULL: stage 0 runs the chain */
 } mp_schnet_forward_desc;
 int mp_schnet_forward_launch(const mp_schnet_forward_desc* desc_host, mpStream_t stream);
 
