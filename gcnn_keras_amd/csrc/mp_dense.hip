@@ -247,7 +247,9 @@ __global__ void softmax_rows_kernel(const float* __restrict__ x, int64_t R, int6
 
 // Keras LayerNormalization over the last axis (kgcnn/layers/norm.py:60-63, 94-105 on the values of a ragged tensor):
 // mean and biased variance of each row (tf.nn.moments: variance as the mean squared difference from the mean), then
-// x * inv + (beta - mean * inv) with inv = rsqrt(var + eps) * gamma (the tf.nn.batch_normalization form Keras uses).
+// (x - mean) * inv + beta with inv = rsqrt(var + eps) * gamma.  Keras' tf.nn.batch_normalization form x * inv + (beta -
+// mean * inv) is the same value, but its two terms of size |mean| * inv cancel: on a row of (near) zero variance inv is
+// rsqrt(eps) and the result carries 2^-24 * |mean| * rsqrt(eps) of absolute error instead of being beta.
 // One wave per row; the row is read twice (L2-resident), reduced with wave shuffles.
 __global__ void layer_norm_rows_kernel(const float* __restrict__ x, int64_t R, int64_t C,
                                        const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
@@ -271,8 +273,7 @@ __global__ void layer_norm_rows_kernel(const float* __restrict__ x, int64_t R, i
     const float rstd = rsqrtf(sq * inv_c + eps);
     for (int64_t c = lane; c < C; c += 64) {
       const float inv = gamma ? rstd * gamma[c] : rstd;
-      const float shift = (beta ? beta[c] : 0.0f) - mean * inv;
-      out[r * C + c] = row[c] * inv + shift;
+      out[r * C + c] = (row[c] - mean) * inv + (beta ? beta[c] : 0.0f);
     }
   }
 }

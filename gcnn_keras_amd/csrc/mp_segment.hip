@@ -169,12 +169,13 @@ __global__ void segment_softmax_csr_kernel(const float* __restrict__ a, int64_t 
 }
 
 __device__ __forceinline__ void atomic_max_f32(float* addr, float v) {
-  // ordered-int trick: valid for all non-NaN floats
-  if (v >= 0.0f) atomicMax(reinterpret_cast<int*>(addr), __float_as_int(v));
+  // ordered-int trick: valid for all non-NaN floats.  The branch goes by the sign BIT: -0.0 compares >= 0 but its pattern
+  // is INT_MIN, which as a signed-int operand loses every max and wins every min (a -0.0 update erased a slot's minimum).
+  if (__float_as_int(v) >= 0) atomicMax(reinterpret_cast<int*>(addr), __float_as_int(v));
   else atomicMin(reinterpret_cast<unsigned int*>(addr), __float_as_uint(v));
 }
 __device__ __forceinline__ void atomic_min_f32(float* addr, float v) {
-  if (v >= 0.0f) atomicMin(reinterpret_cast<int*>(addr), __float_as_int(v));
+  if (__float_as_int(v) >= 0) atomicMin(reinterpret_cast<int*>(addr), __float_as_int(v));
   else atomicMax(reinterpret_cast<unsigned int*>(addr), __float_as_uint(v));
 }
 
