@@ -6,7 +6,7 @@ not on a HIP device, the call fails loudly.
 """
 import ctypes
 import os
-from ctypes import c_char_p, c_float, c_int, c_int64, c_size_t, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_void_p
 
 import torch
 
@@ -20,6 +20,9 @@ MP_PAINN_FILTER_IMAGE_BYTES = 73728   # include/mpengine.h
 MP_CENT_MAX_ATOMS = 128               # include/mpengine.h: atoms per molecule of the charge solve
 MP_SBF_MAX_SPHERICAL, MP_SBF_MAX_RADIAL = 16, 64   # include/mpengine.h: spherical basis limits
 MP_FLAG_OOB, MP_FLAG_UNSORTED_COL0, MP_FLAG_UNSORTED_COL1 = 1, 2, 4
+MP_FLAG_UNKNOWN_SPECIES = 8           # include/mpengine.h: mp_scaler_apply met a species the fit did not see
+MP_DT_F32, MP_DT_F64, MP_DT_I32, MP_DT_I64 = 0, 1, 2, 3
+MP_SCALER_MAX_NUMBER, MP_SCALER_CHUNK_ROWS, MP_SCALER_MAX_STATES = 95, 256, 32   # include/mpengine.h
 
 ACTIVATION_CODES = {
     None: 0, "linear": 0, "relu": 1, "kgcnn>shifted_softplus": 2, "shifted_softplus": 2, "softplus": 3,
@@ -186,6 +189,12 @@ _SIGNATURES = {
                          c_float, P, c_size_t, P, P, P, P],
     "mp_egnn_edge_grad_f32": [P, c_int64, P, P, c_int64, P, P, P, c_int, c_int, P, c_int, P, c_int, P, P, c_int,
                               c_float, P, P, P],
+    "mp_scaler_species_count": [P, c_int, P, c_int64, c_int64, P, P, P, P, P],
+    "mp_scaler_fit_ws_bytes": [c_int64, c_int, P],
+    "mp_scaler_normal_f64": [P, P, c_int64, P, c_int, c_int, P, c_double, c_int, P, P, P, P, c_size_t, P],
+    "mp_scaler_solve_f64": [P, P, P, P, c_int, c_int, P, P, P, P, P],
+    "mp_scaler_residual_std_f64": [P, P, c_int64, P, c_int, c_int, P, P, c_int, P, P, c_size_t, P],
+    "mp_scaler_apply": [P, c_int, P, c_int64, c_int64, c_int, c_int, P, P, P, P, P, c_int, P, c_int, P, P, P, P, P],
 }
 _RESTYPES = {"mp_last_error": c_char_p}
 

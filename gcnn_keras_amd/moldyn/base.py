@@ -15,7 +15,12 @@ post-processors, a list of graphs out (kgcnn/moldyn/base.py:106-165).  MI355X sp
   updates - the step does not go through the packer at all (round 3): the float properties are concatenated into
   persistent pinned blocks and copied straight into the captured graph's input tensors, the graph is replayed, and all
   outputs come back through pinned blocks behind ONE stream synchronisation (0.59 -> 0.32 ms per step for the 21-atom
-  PaiNN case: what remains is the 26-launch energy + force pass itself).
+  PaiNN case: what remains is the 26-launch energy + force pass itself);
+* ``tensor_postprocessors``, the counterpart of ``tensor_preprocessors``, run on the model's OUTPUT tensors on the device,
+  once per call and in front of the read-back - e.g. the inverse label scaling of
+  ``gcnn_keras_amd.graph.postprocessor.ExtensiveEnergyForceScalerPostprocessor``, one launch instead of the reference's
+  ``np.unique`` + ``Ridge.predict`` per molecule and step.  In the replayed step they sit between the graph launch and
+  the pinned copies, so the step keeps its single synchronisation.
 """
 import time
 
@@ -34,14 +39,16 @@ class MolDynamicsModelPredictor:
                  graph_postprocessors=None, store_last_input: bool = False, store_last_output: bool = False,
                  copy_graphs_in_store: bool = False, use_predict: bool = False, batch_size: int = 32,
                  update_from_last_input: list = None, update_from_last_input_skip: int = None,
-                 tensor_preprocessors=None, use_graph: bool = False, device="cuda"):
+                 tensor_preprocessors=None, use_graph: bool = False, device="cuda", tensor_postprocessors=None):
         self.model = model
         self.model_inputs = model_inputs
         self.model_outputs = model_outputs
         self.graph_preprocessors = list(graph_preprocessors or [])
         self.graph_postprocessors = list(graph_postprocessors or [])
         self.tensor_preprocessors = list(tensor_preprocessors or [])
-        for gp in self.graph_preprocessors + self.graph_postprocessors + self.tensor_preprocessors:
+        self.tensor_postprocessors = list(tensor_postprocessors or [])
+        for gp in (self.graph_preprocessors + self.graph_postprocessors + self.tensor_preprocessors
+                   + [getattr(tp, "call_tensors", tp) for tp in self.tensor_postprocessors]):
             if not callable(gp):
                 raise TypeError("pre/post-processors are callables on this engine (serialized configs are not resolved)")
         self.batch_size = batch_size
@@ -139,6 +146,17 @@ class MolDynamicsModelPredictor:
                     d.copy_(s, non_blocking=True)
         return self._graphed[1]()
 
+    def _post_tensors(self, tensor_dict, tensor_input):
+        """``tensor_postprocessors`` on the device: each member (its ``call_tensors`` if it has one) is called with the
+        output tensors by name and the model's input tensors by name, and returns the outputs it replaces or adds."""
+        if not self.tensor_postprocessors:
+            return tensor_dict
+        inputs = {it["name"]: t for it, t in zip(self._items(), tensor_input)}
+        tensor_dict = dict(tensor_dict)
+        for tp in self.tensor_postprocessors:
+            tensor_dict.update(getattr(tp, "call_tensors", tp)(tensor_dict, inputs))
+        return tensor_dict
+
     # ---- same-topology step (use_graph) --------------------------------------------------------------------------
     def _fast_state(self, graph_list):
         """Cache what identifies the bound topology on the host (every integer property of every graph) and make the
@@ -177,7 +195,7 @@ class MolDynamicsModelPredictor:
             np.concatenate(props, axis=0, out=view, casting="unsafe")
             dst.copy_(stage, non_blocking=True)
         out = self._graphed[1]()
-        tensor_dict = self._translate_properties(out, self.model_outputs)
+        tensor_dict = self._post_tensors(self._translate_properties(out, self.model_outputs), self._graphed[2])
         if st["out"] is None:       # pinned blocks for the outputs, one per returned tensor
             st["out"] = {k: torch.empty(tuple((v.values if isinstance(v, RaggedTensor) else v).shape),
                                         dtype=(v.values if isinstance(v, RaggedTensor) else v).dtype, pin_memory=True)
@@ -214,8 +232,9 @@ class MolDynamicsModelPredictor:
 
         host = self._fast_step(graph_list) if self.use_graph else None
         if host is None:
-            tensor_output = self._call_model(self._tensor_input(graph_list))
-            tensor_dict = self._translate_properties(tensor_output, self.model_outputs)
+            tensor_input = self._tensor_input(graph_list)
+            tensor_output = self._call_model(tensor_input)
+            tensor_dict = self._post_tensors(self._translate_properties(tensor_output, self.model_outputs), tensor_input)
             host = {}
             for key, value in tensor_dict.items():
                 host[key] = value.numpy_rows() if isinstance(value, RaggedTensor) else value.detach().cpu().numpy()
