@@ -23,6 +23,9 @@ MP_FLAG_OOB, MP_FLAG_UNSORTED_COL0, MP_FLAG_UNSORTED_COL1 = 1, 2, 4
 MP_FLAG_UNKNOWN_SPECIES = 8           # include/mpengine.h: mp_scaler_apply met a species the fit did not see
 MP_DT_F32, MP_DT_F64, MP_DT_I32, MP_DT_I64 = 0, 1, 2, 3
 MP_SCALER_MAX_NUMBER, MP_SCALER_CHUNK_ROWS, MP_SCALER_MAX_STATES = 95, 256, 32   # include/mpengine.h
+# include/mpengine.h: limits and flag bits of the periodic neighbour search
+MP_PERIODIC_MAX_HITS, MP_PERIODIC_MAX_IMAGE, MP_PERIODIC_MAX_CANDIDATES = 1024, 511, 1048576
+MP_PERIODIC_FLAG_CAPACITY, MP_PERIODIC_FLAG_IMAGE_RANGE, MP_PERIODIC_FLAG_SINGULAR = 1, 2, 4
 
 ACTIVATION_CODES = {
     None: 0, "linear": 0, "relu": 1, "kgcnn>shifted_softplus": 2, "shifted_softplus": 2, "softplus": 3,
@@ -128,6 +131,10 @@ _SIGNATURES = {
     "mp_angle_list_count_i32": [P, c_int64, c_int64, P, P, P, c_int64, c_int, c_int, c_int, c_int, P, P, P, c_size_t, P],
     "mp_angle_list_fill_f32": [P, c_int64, c_int64, P, P, P, P, c_int64, c_int, c_int, c_int, c_int, c_int, P, c_int64,
                                P, P, P, P, P, P, P, P, P, P],
+    "mp_lattice_shift_f32": [P, P, P, P, c_int64, c_int64, P, P],
+    "mp_radius_graph_periodic_workspace_bytes": [c_int64, P],
+    "mp_radius_graph_periodic_count_f32": [P, P, P, c_int64, c_int64, c_float, c_int, P, P, P, P, c_size_t, P],
+    "mp_radius_graph_periodic_fill_f32": [P, P, P, c_int64, c_int64, c_float, c_int, P, c_int64, P, P, P, P, P, P],
     "mp_activation_grad_f32": [c_int, c_float, P, P, c_int64, P, P],
     "mp_sum_axis_f32": [P, c_int64, c_int64, c_int64, c_int, P, P],
     "mp_euclidean_norm_grad_f32": [P, P, c_int64, c_int64, c_int64, c_int, P, P],

@@ -774,6 +774,21 @@ class CosCutoff(torch.autograd.Function):
         return gd, None
 
 
+class LatticeShift(torch.autograd.Function):
+    """``pos + image @ lattice`` per edge (``mp_lattice_shift_f32``).  Linear in the position with unit slope: the reverse
+    is the upstream gradient itself, so the rule is differentiable any number of times.  The lattice gets no gradient
+    (``ShiftPeriodicLattice`` refuses one that requires grad: stress is not implemented)."""
+
+    @staticmethod
+    def forward(ctx, pos, image, lattice, edge_splits):
+        from .layers.geom import _lattice_shift_raw
+        return _lattice_shift_raw(pos, image, lattice, edge_splits)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g, None, None, None
+
+
 # ------------------------------------------------------------------------------------------------ HDNNP2nd
 _coordinate_hessian_discarded = [False]
 

@@ -1,5 +1,5 @@
-"""On-GPU ``SetRange`` and ``SetAngle`` (mirrors of kgcnn/graph/preprocessor.py:255-368 for a ragged batch resident in
-HBM).
+"""On-GPU ``SetRange``, ``SetAngle`` and ``SetRangePeriodic`` (mirrors of kgcnn/graph/preprocessor.py:255-441 for a
+ragged batch resident in HBM).
 
 The reference runs ``define_adjacency_from_distance`` (kgcnn/graph/adj.py:537-593) per molecule in NumPy on the host
 and re-uploads the edge lists; here the whole batch goes through two kernels around one prefix sum
@@ -9,6 +9,10 @@ row (exclusive mode), no self loops, row-major ``(i, j)`` order - hence receiver
 ``SetAngle`` is the second half of the geometry pre-step: the reference loops over the edges of one molecule in Python
 (``get_angle_indices``, kgcnn/graph/adj.py:300-385); here the angle list of the whole batch comes from a count and a
 fill kernel around one prefix sum (csrc/mp_angle.hip), walking the CSR buckets the edge list's index plan already has.
+
+``SetRangePeriodic`` is ``SetRange`` for periodic cells: senders are atoms in periodic images of the cell
+(``range_neighbour_lattice``, kgcnn/graph/geom.py:172-368); one wave per receiver enumerates the exact image box of every
+sender and sorts its hits in LDS (csrc/mp_lattice.hip).
 """
 import torch
 
@@ -203,3 +207,127 @@ class SetAngle:
         angle_edges.attach_plan(range_indices, IndexPlan.from_prepared(angle_edges, range_indices, pcols, pptr,
                                                                        flags=oob | _ffi.MP_FLAG_UNSORTED_COL1))
         return angle_edges, angle_nodes, (RaggedTensor(theta, angle_splits) if self.compute_angles else None)
+
+
+class SetRangePeriodic:
+    """Range connections of a ragged batch of periodic structures, built on the device (``mp_radius_graph_periodic_*``,
+    csrc/mp_lattice.hip).  Keywords and defaults of the reference's ``SetRangePeriodic``
+    (kgcnn/graph/preprocessor.py:393-411).
+
+    Rule (``range_neighbour_lattice``, kgcnn/graph/geom.py:172-368, ``exclusive=True``, ``self_loops=False``): receiver
+    ``i`` is connected to every sender ``j`` in image ``n`` with ``|x_j + n L - x_i| <= max_distance``; only ``(j = i,
+    n = 0)`` is left out, so an atom's own images are neighbours.  Per receiver the neighbours come in ascending
+    distance, cut after ``max_neighbours``; receivers in node order.  The lattice vectors are the rows of ``L``.
+
+    Differences to the reference, both inside what it leaves undefined: the comparison is ``d <= max_distance`` on the
+    float32 distance (the reference adds ``1e-8`` in float64, which is below float32 resolution at these magnitudes), and
+    the order inside a tie - the reference's unstable ``argsort`` - is (float32 distance, sender id, image
+    lexicographic).  Atoms need not be wrapped into the cell.
+
+    Limits: ``MP_PERIODIC_MAX_HITS`` neighbours inside the cutoff per receiver (before the ``max_neighbours`` cut),
+    ``MP_PERIODIC_MAX_CANDIDATES`` image-box candidates per receiver, image indices within ``+-MP_PERIODIC_MAX_IMAGE``,
+    a non-singular lattice.  Exceeding one raises ``ValueError``; nothing is cut silently.
+
+    ``self_loops=True``, ``exclusive=False``, ``do_invert_distance=True`` and ``max_distance=None`` are not implemented.
+    """
+
+    def __init__(self, *, range_indices: str = "range_indices", node_coordinates: str = "node_coordinates",
+                 graph_lattice: str = "graph_lattice", range_image: str = "range_image",
+                 range_attributes: str = "range_attributes", max_distance: float = 4.0, max_neighbours: int = None,
+                 exclusive: bool = True, do_invert_distance: bool = False, self_loops: bool = False,
+                 overwrite: bool = True, name="set_range_periodic", **kwargs):
+        if self_loops or not exclusive or do_invert_distance or max_distance is None:
+            raise NotImplementedError("on-GPU SetRangePeriodic covers: exclusive, no self loops, plain distances, a "
+                                      "finite max_distance")
+        self.name = name
+        self._config_kwargs = {"node_coordinates": node_coordinates, "range_indices": range_indices,
+                               "graph_lattice": graph_lattice, "range_image": range_image,
+                               "range_attributes": range_attributes, "max_distance": max_distance,
+                               "max_neighbours": max_neighbours, "exclusive": exclusive,
+                               "do_invert_distance": do_invert_distance, "self_loops": self_loops,
+                               "overwrite": overwrite}
+        self.max_distance = float(max_distance)
+        self.max_neighbours = max_neighbours
+        self.overwrite = bool(overwrite)
+
+    def get_config(self):
+        return {"name": self.name, **self._config_kwargs}
+
+    @property
+    def produces(self):
+        """Property names this preprocessor adds when used on a dict of packed tensors (MD driver)."""
+        return (self._config_kwargs["range_indices"], self._config_kwargs["range_image"],
+                self._config_kwargs["range_attributes"])
+
+    def __call__(self, node_coordinates, graph_lattice=None, range_indices=None, range_image=None):
+        """``(node_coordinates, graph_lattice)`` -> ``(range_indices, range_image, range_attributes)``, or a dict of packed
+        device tensors -> dict of the three properties.  With ``overwrite=False`` and both ``range_indices`` and
+        ``range_image`` given (as arguments, or present in the dict) only the distances are recomputed."""
+        if isinstance(node_coordinates, dict):
+            t, cfg = node_coordinates, self._config_kwargs
+            out = self._dispatch(t[cfg["node_coordinates"]], t[cfg["graph_lattice"]], t.get(cfg["range_indices"]),
+                                 t.get(cfg["range_image"]))
+            return {name: v for name, v in zip(self.produces, out)}
+        return self._dispatch(node_coordinates, graph_lattice, range_indices, range_image)
+
+    def _dispatch(self, xyz, lattice, indices, image):
+        if lattice is None:
+            raise ValueError("SetRangePeriodic needs the lattice matrices (batch, 3, 3)")
+        if not self.overwrite and indices is not None and image is not None:
+            return indices, image, self._distances(xyz, lattice, indices, image)
+        return self._run(xyz, lattice)
+
+    @staticmethod
+    def _check(node_coordinates, graph_lattice):
+        xyz = node_coordinates.values.contiguous()
+        _ffi.require_device(xyz, node_coordinates.row_splits, graph_lattice)
+        g = node_coordinates.nrows()
+        if xyz.dtype != torch.float32 or graph_lattice.dtype != torch.float32:
+            raise TypeError("SetRangePeriodic expects float32 coordinates and lattice")
+        if tuple(graph_lattice.shape) != (g, 3, 3):
+            raise ValueError("graph_lattice must have shape (%d, 3, 3), got %s" % (g, tuple(graph_lattice.shape)))
+        return xyz, graph_lattice.contiguous(), g
+
+    @staticmethod
+    def _distances(node_coordinates, graph_lattice, range_indices, range_image):
+        """``range_attributes`` of a given edge list: gather, shift, norm - the layers the crystal models run."""
+        from ..layers.geom import NodeDistanceEuclidean, NodePosition, ShiftPeriodicLattice
+        with torch.no_grad():
+            pos1, pos2 = NodePosition()([node_coordinates, range_indices])
+            pos2 = ShiftPeriodicLattice()([pos2, range_image, graph_lattice])
+            return NodeDistanceEuclidean()([pos1, pos2])
+
+    def _run(self, node_coordinates: RaggedTensor, graph_lattice):
+        """``node_coordinates``: ragged ``(batch, [N], 3)`` float32; ``graph_lattice``: ``(batch, 3, 3)`` float32.
+        Returns ragged ``(batch, [M], 2)`` int64 sample indices carrying a ready index plan (column 0 sorted, column 1 not
+        claimed), ragged ``(batch, [M], 3)`` int64 images and ragged ``(batch, [M], 1)`` float32 distances."""
+        from ..ragged import IndexPlan
+        xyz, lat, g = self._check(node_coordinates, graph_lattice)
+        n, dev = int(xyz.shape[0]), xyz.device
+        mn = -1 if self.max_neighbours is None else int(min(self.max_neighbours, 2 ** 30))
+        nbytes = _ffi.workspace_bytes("mp_radius_graph_periodic_workspace_bytes", n)
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        head = torch.empty(n + 2, dtype=torch.int32, device=dev)   # node_ptr (N+1), then the flag word
+        node_ptr, flags = head[:n + 1], head[n + 1:]
+        edge_splits = torch.empty(g + 1, dtype=torch.int64, device=dev)
+        _ffi.call("mp_radius_graph_periodic_count_f32", _ffi.ptr(xyz), _ffi.ptr(node_coordinates.row_splits),
+                  _ffi.ptr(lat), g, n, self.max_distance, mn, _ffi.ptr(node_ptr), _ffi.ptr(edge_splits),
+                  _ffi.ptr(flags), _ffi.ptr(ws), nbytes, _ffi.stream())
+        m, bits = (int(v) for v in head[n:].tolist())   # the one host read: output size and limit flags together
+        if bits:
+            raise ValueError("SetRangePeriodic(max_distance=%g): %s" % (self.max_distance, "; ".join(
+                text for bit, text in (
+                    (_ffi.MP_PERIODIC_FLAG_CAPACITY, "a receiver has more than %d neighbours inside the cutoff or more "
+                     "than %d image candidates" % (_ffi.MP_PERIODIC_MAX_HITS, _ffi.MP_PERIODIC_MAX_CANDIDATES)),
+                    (_ffi.MP_PERIODIC_FLAG_IMAGE_RANGE, "an image index exceeds +-%d" % _ffi.MP_PERIODIC_MAX_IMAGE),
+                    (_ffi.MP_PERIODIC_FLAG_SINGULAR, "a lattice is singular (cell volume ~ 0)")) if bits & bit)))
+        idx = torch.empty((m, 2), dtype=torch.int64, device=dev)
+        image = torch.empty((m, 3), dtype=torch.int64, device=dev)
+        cols = torch.empty((2, max(m, 1)), dtype=torch.int32, device=dev)
+        dist = torch.empty((m, 1), dtype=torch.float32, device=dev)
+        _ffi.call("mp_radius_graph_periodic_fill_f32", _ffi.ptr(xyz), _ffi.ptr(node_coordinates.row_splits),
+                  _ffi.ptr(lat), g, n, self.max_distance, mn, _ffi.ptr(node_ptr), m, _ffi.ptr(idx), _ffi.ptr(image),
+                  _ffi.ptr(cols[0]), _ffi.ptr(cols[1]), _ffi.ptr(dist), _ffi.stream())
+        indices = RaggedTensor(idx, edge_splits)
+        indices.attach_plan(node_coordinates, IndexPlan.from_prepared(indices, node_coordinates, cols, node_ptr))
+        return indices, RaggedTensor(image, edge_splits), RaggedTensor(dist, edge_splits)

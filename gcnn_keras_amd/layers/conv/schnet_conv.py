@@ -55,6 +55,9 @@ class SchNetCFconv(GraphBaseLayer):
         self.lay_mult = LazyMultiply()
         self._packed = None  # LDS image of the filter weights for the fused kernel (rebuilt when weights change)
         self._packed_key = None
+        # True: the fused kernel's bit-reproducible mode (mp_cfconv_fused_ws_f32, one extra launch); set by the crystal
+        # builder, whose receivers have more than 32 edges.  Not a constructor keyword: get_config() stays the reference's.
+        self.deterministic = False
 
     def build(self, input_shape):
         super().build(input_shape)
@@ -113,6 +116,16 @@ class SchNetCFconv(GraphBaseLayer):
         _, perm, recv_sorted = plan.csr(0, assume_sorted=self.lay_sum.is_sorted)
         basis = int(edge.values.shape[1])
         out = torch.zeros((plan.N, 128), dtype=torch.float32, device=node.values.device)
+        if self.deterministic:
+            # receivers with more than 32 edges (periodic cells): the partial rows of a receiver that spans several tiles
+            # are parked in a workspace and added in edge order by a second small kernel instead of with float atomics
+            nbytes = _ffi.workspace_bytes("mp_cfconv_det_workspace_bytes", plan.M)
+            ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=node.values.device)
+            _ffi.call("mp_cfconv_fused_ws_f32", _ffi.ptr(node.values.contiguous()), plan.N,
+                      _ffi.ptr(edge.values.contiguous()), basis, _ffi.ptr(self._packed_weights(basis)),
+                      _ffi.ptr(recv_sorted.contiguous()), _ffi.ptr(plan.col(1).contiguous()), _ffi.ptr(perm), plan.M,
+                      1 | 32, _ffi.ptr(out), _ffi.ptr(ws), nbytes, _ffi.stream())
+            return node.with_values(out)
         _ffi.call("mp_cfconv_fused_f32", _ffi.ptr(node.values.contiguous()), plan.N, _ffi.ptr(edge.values.contiguous()),
                   basis, _ffi.ptr(self._packed_weights(basis)), _ffi.ptr(recv_sorted.contiguous()),
                   _ffi.ptr(plan.col(1).contiguous()), _ffi.ptr(perm), plan.M, 1, _ffi.ptr(out), _ffi.stream())

@@ -42,6 +42,51 @@ def _rdc(values, axis_values):
     return r, shape[axis_values], c
 
 
+def _lattice_shift_raw(pos, image, lattice, edge_splits):
+    _ffi.require_device(pos, image, lattice, edge_splits)
+    p, im, lat = pos.contiguous(), image.contiguous(), lattice.contiguous()
+    m, g = int(p.shape[0]), int(lat.shape[0])
+    out = torch.empty_like(p)
+    _ffi.call("mp_lattice_shift_f32", _ffi.ptr(p), _ffi.ptr(im), _ffi.ptr(lat), _ffi.ptr(edge_splits), g, m,
+              _ffi.ptr(out), _ffi.stream())
+    return out
+
+
+class ShiftPeriodicLattice(GraphBaseLayer):
+    r"""``x + n_1 a_1 + n_2 a_2 + n_3 a_3`` for positions ``x`` ``(batch, [M], 3)``, image indices ``n``
+    ``(batch, [M], 3)`` int64 and one lattice matrix ``(batch, 3, 3)`` per graph, lattice vectors in rows
+    (kgcnn/layers/geom.py:76-123).  The sum runs in the reference's order, ``x + ((n_1 a_1 + n_2 a_2) + n_3 a_3)``,
+    without contraction.  The output carries the partition of the image tensor.  Linear in the position; a lattice that
+    requires grad raises (stress is not implemented)."""
+
+    weight_gradients = True   # layers/base.py: no weight of this layer is left off the tape
+
+    def call(self, inputs, **kwargs):
+        from ..ragged import RaggedTensor
+        if len(inputs) != 3:
+            raise ValueError("ShiftPeriodicLattice expects [position, edge_image, lattice]")
+        x, ei, lattice = inputs
+        if not isinstance(x, RaggedTensor) or not isinstance(ei, RaggedTensor):
+            raise TypeError("ShiftPeriodicLattice expects ragged positions and ragged image indices")
+        if isinstance(lattice, RaggedTensor) or not torch.is_tensor(lattice):
+            raise TypeError("ShiftPeriodicLattice expects the lattice as a dense tensor of shape (batch, 3, 3)")
+        if ei.values.dtype != torch.int64:
+            raise TypeError("edge_image must be int64, got %s" % ei.values.dtype)
+        if x.values.dtype != torch.float32 or lattice.dtype != torch.float32:
+            raise TypeError("ShiftPeriodicLattice expects float32 positions and lattice")
+        if tuple(lattice.shape) != (ei.nrows(), 3, 3):
+            raise ValueError("lattice must have shape (%d, 3, 3), got %s" % (ei.nrows(), tuple(lattice.shape)))
+        if tuple(x.values.shape) != tuple(ei.values.shape) or x.values.dim() != 2 or int(x.values.shape[1]) != 3:
+            raise ValueError("positions %s and images %s must both be (batch, [M], 3)"
+                             % (tuple(x.values.shape), tuple(ei.values.shape)))
+        if lattice.requires_grad and torch.is_grad_enabled():
+            raise NotImplementedError("gradients with respect to the lattice (stress) are not implemented")
+        from ..autograd import LatticeShift, needs_grad
+        if needs_grad(x.values):
+            return ei.with_values(LatticeShift.apply(x.values, ei.values, lattice, ei.row_splits))
+        return ei.with_values(_lattice_shift_raw(x.values, ei.values, lattice, ei.row_splits))
+
+
 class EuclideanNorm(GraphBaseLayer):
     r"""``sqrt(relu(sum_axis x^2))`` with optional eps / inversion (kgcnn/layers/geom.py:127-214)."""
 

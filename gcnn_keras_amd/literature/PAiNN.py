@@ -1,9 +1,11 @@
-"""PaiNN model builder (mirror of kgcnn/literature/PAiNN.py:24-155, ``make_model``; crystal variant and the
-normalisation branches are out of scope)."""
+"""PaiNN model builders (mirror of kgcnn/literature/PAiNN.py:24-298, ``make_model`` and ``make_crystal_model``; the
+normalisation branches are out of scope).  ``make_crystal_model`` takes ``[node_attributes, node_coordinates,
+bond_indices, edge_image, graph_lattice]`` (+ optional ``equiv_initial``), shifts the sender position of every edge by
+``edge_image @ lattice`` and always runs the layer path, replayed from one HIP graph per bound batch."""
 from ..layers.casting import ChangeTensorType
 from ..layers.conv.painn_conv import EquivariantInitialize, PAiNNconv, PAiNNUpdate
 from ..layers.geom import (BesselBasisLayer, CosCutOffEnvelope, EdgeDirectionNormalized, NodeDistanceEuclidean,
-                           NodePosition)
+                           NodePosition, ShiftPeriodicLattice)
 from ..layers.mlp import MLP, GraphMLP
 from ..layers.modules import LazyAdd, OptionalInputEmbedding
 from ..layers.pooling import PoolingNodes
@@ -32,6 +34,28 @@ model_default = {
     "output_mlp": {"use_bias": [True, True], "units": [128, 1], "activation": ["swish", "linear"]}
 }
 
+model_crystal_default = {
+    "name": "PAiNN",
+    "inputs": [
+        {"shape": (None,), "name": "node_attributes", "dtype": "float32", "ragged": True},
+        {"shape": (None, 3), "name": "node_coordinates", "dtype": "float32", "ragged": True},
+        {"shape": (None, 2), "name": "edge_indices", "dtype": "int64", "ragged": True},
+        {"shape": (None, 3), "name": "edge_image", "dtype": "int64", "ragged": True},
+        {"shape": (3, 3), "name": "graph_lattice", "dtype": "float32", "ragged": False}
+    ],
+    "input_embedding": {"node": {"input_dim": 95, "output_dim": 128}},
+    "equiv_initialize_kwargs": {"dim": 3, "method": "zeros"},
+    "bessel_basis": {"num_radial": 20, "cutoff": 5.0, "envelope_exponent": 5},
+    "pooling_args": {"pooling_method": "sum"},
+    "conv_args": {"units": 128, "cutoff": None, "conv_pool": "sum"},
+    "update_args": {"units": 128},
+    "equiv_normalization": False, "node_normalization": False,
+    "depth": 3,
+    "verbose": 10,
+    "output_embedding": "graph", "output_to_tensor": True,
+    "output_mlp": {"use_bias": [True, True], "units": [128, 1], "activation": ["swish", "linear"]}
+}
+
 
 @update_model_kwargs(model_default)
 def make_model(inputs: list = None, input_embedding: dict = None, equiv_initialize_kwargs: dict = None,
@@ -41,13 +65,40 @@ def make_model(inputs: list = None, input_embedding: dict = None, equiv_initiali
                output_mlp: dict = None):
     r"""Build PaiNN (kgcnn/literature/PAiNN.py:45-155).  Model inputs ``[node_attributes, node_coordinates,
     bond_indices]`` (+ optional ``equiv_initial``); output ``(batch, L)`` for ``output_embedding="graph"``."""
+    return _make(False, inputs, input_embedding, equiv_initialize_kwargs, bessel_basis, depth, pooling_args, conv_args,
+                 update_args, equiv_normalization, node_normalization, name, output_embedding, output_to_tensor,
+                 output_mlp)
+
+
+@update_model_kwargs(model_crystal_default)
+def make_crystal_model(inputs: list = None, input_embedding: dict = None, equiv_initialize_kwargs: dict = None,
+                       bessel_basis: dict = None, depth: int = None, pooling_args: dict = None, conv_args: dict = None,
+                       update_args: dict = None, equiv_normalization: bool = None, node_normalization: bool = None,
+                       name: str = None, verbose: int = None, output_embedding: str = None,
+                       output_to_tensor: bool = None, output_mlp: dict = None):
+    r"""Build PaiNN for periodic structures (kgcnn/literature/PAiNN.py:181-298).  Model inputs ``[node_attributes,
+    node_coordinates, bond_indices, edge_image, graph_lattice]`` (+ optional ``equiv_initial``); ``edge_image`` ragged
+    ``(batch, [M], 3)`` int64, ``graph_lattice`` dense ``(batch, 3, 3)`` with the lattice vectors in rows."""
+    if inputs is None or len(inputs) < 5:
+        raise ValueError("PAiNN.make_crystal_model needs five inputs (node, xyz, edge_indices, edge_image, "
+                         "graph_lattice) as in model_crystal_default[\"inputs\"]")
+    return _make(True, inputs, input_embedding, equiv_initialize_kwargs, bessel_basis, depth, pooling_args, conv_args,
+                 update_args, equiv_normalization, node_normalization, name, output_embedding, output_to_tensor,
+                 output_mlp)
+
+
+def _make(crystal, inputs, input_embedding, equiv_initialize_kwargs, bessel_basis, depth, pooling_args, conv_args,
+          update_args, equiv_normalization, node_normalization, name, output_embedding, output_to_tensor, output_mlp):
+    """Both builders: the same layers in the same order; ``crystal`` adds the lattice shift of the sender positions."""
+    n_base = 5 if crystal else 3   # inputs in front of the optional equiv_initial
     if equiv_normalization or node_normalization:
         raise NotImplementedError("GraphLayerNormalization / GraphBatchNormalization are outside the hot path")
     if output_embedding not in ("graph", "node"):
         raise ValueError("Unsupported output embedding for mode `PAiNN`")
     embed = OptionalInputEmbedding(**input_embedding["node"], use_embedding=len(inputs[0]["shape"]) < 2)
-    equiv_init = EquivariantInitialize(**equiv_initialize_kwargs) if len(inputs) <= 3 else None
+    equiv_init = EquivariantInitialize(**equiv_initialize_kwargs) if len(inputs) <= n_base else None
     lay_pos, lay_dir, lay_dist = NodePosition(), EdgeDirectionNormalized(), NodeDistanceEuclidean()
+    lay_shift = ShiftPeriodicLattice() if crystal else None
     lay_env = CosCutOffEnvelope(conv_args["cutoff"])
     lay_rbf = BesselBasisLayer(**bessel_basis)
     convs = [PAiNNconv(**conv_args) for _ in range(depth)]
@@ -68,8 +119,10 @@ def make_model(inputs: list = None, input_embedding: dict = None, equiv_initiali
             raise ValueError("this PAiNN configuration / these inputs do not fit the fused pipeline")
         node_input, xyz_input, edi = model_inputs[:3]
         z = embed(node_input)
-        v = model_inputs[3] if len(model_inputs) > 3 else equiv_init(z)
+        v = model_inputs[n_base] if len(model_inputs) > n_base else equiv_init(z)
         pos1, pos2 = lay_pos([xyz_input, edi])
+        if crystal:
+            pos2 = lay_shift([pos2, model_inputs[3], model_inputs[4]])
         rij = lay_dir([pos1, pos2])
         d = lay_dist([pos1, pos2])
         env = lay_env(d)
@@ -118,9 +171,10 @@ def make_model(inputs: list = None, input_embedding: dict = None, equiv_initiali
               "update_args": update_args, "equiv_normalization": equiv_normalization,
               "node_normalization": node_normalization, "output_embedding": output_embedding, "output_mlp": output_mlp}
     route = None
-    if _fused.supports(merged) and embed.use_embedding:
+    if not crystal and _fused.supports(merged) and embed.use_embedding:
         route = _fused.PainnFusedRoute(fused_tensors, merged)
-    model = Model(name, forward, layers, config={"depth": depth, "conv_args": conv_args, "update_args": update_args})
+    model = Model(name, forward, layers, config={"depth": depth, "conv_args": conv_args, "update_args": update_args},
+                  auto_graph=crystal)
     model.__kgcnn_model_version__ = __model_version__
     model.fused = route   # None: this configuration always runs the layer path
     return model

@@ -611,3 +611,22 @@ def egnn_params(model, seed=14):
             v = glorot_uniform(rng, shape[0], shape[-1], shape=shape)
         p["%03d/%s" % (i, name)] = np.asarray(v, dtype=np.float32)
     return p
+
+
+def periodic_structures(num_graphs=128, seed=5678, min_atoms=4, max_atoms=30, density=0.07, skew=0.1):
+    """Random periodic structures for the periodic-cell measurements: per structure ``n`` atoms (uniform in
+    ``[min_atoms, max_atoms]``) at uniform fractional positions in a cell of volume about ``n / density`` (atoms per
+    cubic Angstrom; 0.07 is typical of inorganic crystals), ``edge * (I + skew * uniform(-1, 1, (3, 3)))`` with the
+    lattice vectors in rows.  Returns ``node_number`` (int64), ``node_coordinates`` (float32), ``node_splits`` and
+    ``graph_lattice`` ``(G, 3, 3)`` float32."""
+    rng = np.random.default_rng(seed)
+    sizes = rng.integers(min_atoms, max_atoms + 1, size=num_graphs)
+    numbers, coords, lattices = [], [], []
+    for n in sizes:
+        edge = (float(n) / density) ** (1.0 / 3.0)
+        lat = edge * (np.eye(3) + skew * rng.uniform(-1.0, 1.0, size=(3, 3)))
+        coords.append((rng.uniform(0.0, 1.0, size=(int(n), 3)) @ lat).astype(np.float32))
+        lattices.append(lat.astype(np.float32))
+        numbers.append(rng.choice(np.array([1, 6, 7, 8, 14], dtype=np.int64), size=int(n)))
+    return {"node_number": np.concatenate(numbers), "node_coordinates": np.concatenate(coords, axis=0),
+            "node_splits": _splits(sizes), "graph_lattice": np.stack(lattices)}

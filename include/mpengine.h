@@ -508,6 +508,37 @@ int mp_angle_list_fill_f32(const int32_t* edge_cols, int64_t M, int64_t N, const
                            int32_t* pair_cols, float* theta, const int32_t* edge_ptr0, int32_t* triple_ptr,
                            int32_t* pair_ptr, mpStream_t stream);
 
+/* ---------------------------------------------------------------- periodic cells ------------------------- */
+/* ShiftPeriodicLattice.call, kgcnn/layers/geom.py:100-123: out[e] = pos[e] + ((n0 a0 + n1 a1) + n2 a2) with
+ * n = image[e] (M,3) int64 and a_k the rows of lattice[g(e)] (G,3,3), g(e) from the edge row_splits (G+1); the
+ * reference's reduce_sum order, no contraction.  M == 0 returns MP_OK without touching the device.
+ *
+ * SetRangePeriodic.call, kgcnn/graph/preprocessor.py:413-441 via range_neighbour_lattice (kgcnn/graph/geom.py:172-368),
+ * exclusive mode, no self loops, for a ragged batch of coordinates xyz (N,3) with one cell lattice (G,3,3) per graph
+ * (lattice vectors in rows).  Receiver i is connected to every (sender j, image n) with |(x_j + n L) - x_i| <=
+ * max_distance in float32 (the shift as above), except (j = i, n = 0); per receiver in the order (distance, sender,
+ * image lexicographic), cut after max_neighbours (< 0: no cut); receivers in node order.  Pass 1 writes node_ptr (N+1)
+ * int32 = receiver CSR, edge_splits (G+1) int64 and the flag word (zeroed first, then mp_periodic_flag bits; a receiver
+ * that raised one counts no edge); the caller reads M = node_ptr[N] and the flag word to size the outputs.  Pass 2
+ * writes the (M,2) int64 sample indices (i, j), the (M,3) int64 images and, each nullable, the int32 receiver / sender
+ * ids and the distances (range_attributes).  max_distance must be finite and >= 0.  As in mp_radius_graph_*, node_ptr is
+ * int32: the caller keeps N x degree below 2^31 (2^31 edges are 50 GB of outputs). */
+#define MP_PERIODIC_MAX_HITS 1024           /* neighbours inside the cutoff per receiver, before the max_neighbours cut */
+#define MP_PERIODIC_MAX_IMAGE 511           /* |n_k| of an image index */
+#define MP_PERIODIC_MAX_CANDIDATES 1048576  /* (sender, image) candidates of the image boxes per receiver */
+enum mp_periodic_flag { MP_PERIODIC_FLAG_CAPACITY = 1, MP_PERIODIC_FLAG_IMAGE_RANGE = 2, MP_PERIODIC_FLAG_SINGULAR = 4 };
+int mp_lattice_shift_f32(const float* pos, const int64_t* image, const float* lattice, const int64_t* edge_splits,
+                         int64_t G, int64_t M, float* out, mpStream_t stream);
+int mp_radius_graph_periodic_workspace_bytes(int64_t N, size_t* bytes_out_host);
+int mp_radius_graph_periodic_count_f32(const float* xyz, const int64_t* node_splits, const float* lattice, int64_t G,
+                                       int64_t N, float max_distance, int max_neighbours, int32_t* node_ptr,
+                                       int64_t* edge_splits, int32_t* flags, void* ws, size_t ws_bytes,
+                                       mpStream_t stream);
+int mp_radius_graph_periodic_fill_f32(const float* xyz, const int64_t* node_splits, const float* lattice, int64_t G,
+                                      int64_t N, float max_distance, int max_neighbours, const int32_t* node_ptr,
+                                      int64_t M, int64_t* idx_out, int64_t* image_out, int32_t* recv, int32_t* send,
+                                      float* dist, mpStream_t stream);
+
 /* ---------------------------------------------------------------- backward helpers (forces) -------------- */
 /* EnergyForceModel, kgcnn/model/force.py:159-186: F = -dE/dx needs one reverse pass.  Gather-backward is
  * mp_segment_reduce_csr_f32 over the CSR of the gathered column, segment-sum-backward is mp_gather_rows_f32 by the
