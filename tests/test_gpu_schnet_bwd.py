@@ -1,6 +1,8 @@
-"""Reverse node chains of the SchNet energy + force pass (csrc/mp_schnet_bwd.hip) and the SAVE builds of the forward
-chains, through the C-ABI, against float64 torch arithmetic of the same formulas on the CPU.  f32 tolerance written per
-test (k-ordered fma chains of length <= 128: 2e-5 of the output scale)."""
+"""Reverse node chains, force kernel and distance gradient of the SchNet energy + force pass (csrc/mp_schnet_bwd.hip,
+csrc/mp_cfconv_bwd.hip) on molecular shapes, through the C-ABI, against float64 arithmetic of the same formulas on the
+CPU.  f32 tolerance written per test (k-ordered fma chains of length <= 128: 2e-5 of the output scale).  The SAVE builds
+of the forward chains, the readout with dE/dpooled and the tile, trip and basis edges of these kernels are tested in
+tests/test_gpu_schnet_force_edges.py."""
 import numpy as np
 import pytest
 import torch

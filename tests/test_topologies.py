@@ -58,6 +58,26 @@ def test_tile_exact_sizes():
             assert e.min() >= 0 and e.max() < n and np.all(np.diff(e[:, 0]) >= 0) and np.all(e[:, 0] != e[:, 1])
 
 
+def test_swap_columns_moves_the_hubs_to_the_sender_side():
+    e = T.hub_edges(260, T.STANDARD_DEGREES, seed=3)
+    s = T.swap_columns(e)
+    assert s.shape == e.shape and s.dtype == np.int64 and s.flags["C_CONTIGUOUS"]
+    assert np.array_equal(s[:, 0], e[:, 1]) and np.array_equal(s[:, 1], e[:, 0])
+    assert np.all(np.diff(s[:, 1]) >= 0) and np.any(np.diff(s[:, 0]) < 0)
+    assert np.array_equal(T.in_degrees(s, 260, column=1), T.in_degrees(e, 260, column=0))
+
+
+def test_ring_edges_leave_the_other_nodes_isolated():
+    n, step = 8209, 3
+    e = T.ring_edges(n, step)
+    ring = np.arange(0, n, step)
+    assert e.shape == (len(ring), 2) and e.dtype == np.int64 and np.all(np.diff(e[:, 0]) > 0)
+    assert np.all(e[:, 0] != e[:, 1]) and tuple(e[-1]) == (ring[-1], 0)
+    for column in (0, 1):
+        deg = T.in_degrees(e, n, column=column)
+        assert np.all(deg[ring] == 1) and deg.sum() == len(ring)          # everything off the ring is isolated
+
+
 @pytest.mark.parametrize("order", ["sorted", "shuffled"])
 def test_hub_triplets_counts(order):
     a = T.hub_triplets(300, T.STANDARD_TRIPLET_COUNTS, seed=11, order=order)

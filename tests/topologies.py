@@ -63,6 +63,20 @@ def tile_exact(total, n=5, seed=0):
     return n, np.stack([recv, send], axis=-1).astype(np.int64).reshape(-1, 2)
 
 
+def swap_columns(edges):
+    """The same pairs with receiver and sender exchanged: a list sorted by receiver becomes one sorted by sender, and the
+    in-degrees of the first column become those of the second."""
+    return np.ascontiguousarray(np.asarray(edges)[:, ::-1])
+
+
+def ring_edges(n, step):
+    """Edge list ``(E, 2)`` int64, sorted by receiver, of a ring over every ``step``-th node of ``n``: node ``step * k``
+    receives from its successor on the ring (the last one from node 0); every other node is isolated on both columns."""
+    assert step >= 2 and n > 2 * step, (n, step)
+    ring = np.arange(0, n, step)
+    return np.stack([ring, np.roll(ring, -1)], axis=-1).astype(np.int64).reshape(-1, 2)
+
+
 def hub_triplets(num_edges, counts, seed, order="sorted"):
     """Angle pairs ``(T, 2)`` int64 ``[n, m]`` over ``num_edges`` edges: ``len(counts)`` receiving edges ``n`` (ascending,
     spread) with exactly these numbers of triplets, partners ``m != n`` drawn at random; other edges receive none."""
