@@ -1218,7 +1218,7 @@ __global__ __launch_bounds__(256, 2) void painn_message_bwd_tile_kernel(PainnBwd
         // beyond the bias slot read the zero units
         const bool rv = 2 * uA + hA < nh;
         const int rowu = __umul24(2 * (lo + cb + 2 * uA + hA) + kind, 3 * NG);
-        const int u0 = rv ? rowu + 3 * hh : zunit;
+        const int u0 = (rv && hh < NG) ? rowu + 3 * hh : zunit;   // (B <= 7: one k group, the upper lane half has none)
         const int u1 = (rv && 2 + hh < NG) ? rowu + 6 + 3 * hh : zunit;
         bf16x8 qa[2][3];
 #pragma unroll

@@ -58,6 +58,28 @@ def test_tile_exact_sizes():
             assert e.min() >= 0 and e.max() < n and np.all(np.diff(e[:, 0]) >= 0) and np.all(e[:, 0] != e[:, 1])
 
 
+def test_degree_edges_put_the_degrees_on_consecutive_nodes():
+    degrees = (0, 1, 7, 16, 17, 0, 40, 3)
+    for n, first in ((12, 0), (12, 4), (50, 21)):
+        e = T.degree_edges(n, degrees, seed=4, first=first)
+        assert e.shape == (sum(degrees), 2) and e.dtype == np.int64 and np.all(np.diff(e[:, 0]) >= 0)
+        assert e.min() >= 0 and e.max() < n and np.all(e[:, 0] != e[:, 1])
+        deg = T.in_degrees(e, n)
+        assert tuple(deg[first:first + len(degrees)]) == degrees and deg.sum() == sum(degrees)
+        for k, d in enumerate(degrees):                      # senders repeat only where the degree exceeds n - 1
+            s = e[e[:, 0] == first + k, 1]
+            assert (len(np.unique(s)) == d) == (d <= n - 1)
+    assert T.degree_edges(5, (), seed=0).shape == (0, 2)
+
+
+def test_two_neighbour_edges_have_degree_two_on_both_columns():
+    for n in (3, 5, 47, 63):
+        e = T.two_neighbour_edges(n)
+        assert e.shape == (2 * n, 2) and e.dtype == np.int64 and np.all(np.diff(e[:, 0]) >= 0)
+        assert np.all(e[:, 0] != e[:, 1]) and len(np.unique(e, axis=0)) == 2 * n
+        assert np.all(T.in_degrees(e, n, 0) == 2) and np.all(T.in_degrees(e, n, 1) == 2)
+
+
 def test_swap_columns_moves_the_hubs_to_the_sender_side():
     e = T.hub_edges(260, T.STANDARD_DEGREES, seed=3)
     s = T.swap_columns(e)

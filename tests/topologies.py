@@ -54,6 +54,29 @@ def hub_edges(n, degrees, seed, self_loops=False, duplicates=False, order="sorte
     return e
 
 
+def degree_edges(n, degrees, seed, first=0):
+    """Edge list ``(E, 2)`` int64 ``[receiver, sender]``, sorted by receiver, of one graph of ``n`` nodes: the CONSECUTIVE
+    nodes ``first, first + 1, ...`` have exactly these in-degrees (0 allowed), every other node receives nothing; senders
+    drawn at random among the other nodes (a degree above ``n - 1`` repeats senders).  ``hub_edges`` spreads its
+    receivers; kernels that walk receivers in pairs or tiles need the degrees side by side."""
+    assert first >= 0 and first + len(degrees) <= n, (n, first, len(degrees))
+    rng = np.random.default_rng(seed)
+    rows = [np.zeros((0, 2), np.int64)]
+    for k, deg in enumerate(degrees):
+        others = np.delete(np.arange(n), first + k)
+        s = rng.choice(others, size=deg, replace=deg > len(others))
+        rows.append(np.stack([np.full(deg, first + k), s], axis=-1).astype(np.int64).reshape(-1, 2))
+    return np.concatenate(rows, axis=0)
+
+
+def two_neighbour_edges(n):
+    """Edge list sorted by receiver in which node ``i`` of ``n >= 3`` receives from ``i + 1`` and ``i + 2`` (modulo ``n``):
+    degree 2 on both columns, no self loops."""
+    assert n >= 3, n
+    i = np.repeat(np.arange(n), 2)
+    return np.stack([i, (i + np.tile([1, 2], n)) % n], axis=-1).astype(np.int64)
+
+
 def tile_exact(total, n=5, seed=0):
     """``(n, edges)``: a graph of ``n`` nodes with exactly ``total`` edges, sorted by receiver (``total = 0``: nodes
     only, the finishing pass alone runs)."""
