@@ -95,7 +95,6 @@ _SIGNATURES = {
     "mp_cfconv_bwd_pack_f32": [P, P, c_int, P, P, P],
     "mp_cfconv_gauss_dist_grad_f32": [P, P, c_int64, P, c_int, c_float, c_float, c_float, P, P, P, c_int64, c_int, P, P],
     "mp_cfconv_gauss_diag_f32": [P, c_int64, P, c_int, c_float, c_float, c_float, P, P, P, P, c_int64, P, P, P],
-    "mp_painn_message_fused_f32": [P, P, c_int64, P, c_int, P, P, P, P, P, P, P, c_int64, P, P, P],
     "mp_lstm_zero_state_f32": [P, c_int64, c_int64, c_int, c_int, P, P],
     "mp_gru_combine_f32": [P, P, P, c_int64, c_int64, c_int, c_int, P, P],
     "mp_batched_matvec_f32": [P, P, c_int64, c_int64, c_int64, P, P],

@@ -47,7 +47,6 @@
 //    matrix work are written for instruction count (packed FP32, scalar control, 6-instruction softplus).
 //  * The output buffer must be zero on entry (unconnected nodes keep 0 = the has_unconnected pad of
 //    kgcnn/layers/pooling.py:74-76).
-#include <mutex>
 #include <type_traits>
 
 #include "mp_common.h"
@@ -120,8 +119,8 @@ struct CfconvArgs {
     t_prev = t_now;                                                                    \
   }
 
-template <int WAVES, bool GAUSS, bool FAST_SSP, int NKT, bool DIAG = false, bool COMPACT = false>
-__global__ __launch_bounds__(WAVES * 64, (WAVES == 4 && COMPACT) ? 2 : 1) void cfconv_fused_kernel(CfconvArgs a) {
+template <int WAVES, bool GAUSS, bool FAST_SSP, int NKT, bool DIAG = false>
+__global__ __launch_bounds__(WAVES * 64, 1) void cfconv_fused_kernel(CfconvArgs a) {
   unsigned long long diag_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   unsigned long long t_prev = 0;
   if constexpr (DIAG) t_prev = __builtin_amdgcn_s_memtime();
@@ -223,8 +222,7 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 4 && COMPACT) ? 2 : 1) void c
   // A wave WITH a tile has, at the barrier, issued behind the weight requests: the loads of its edge data (waited for
   // at tile start - which drains the requests, too), then (sender rows at tile start) 16 row loads and 0-4 loads of the
   // next tile's edge data.  "All but the youngest 16" therefore covers the weights and leaves the rows in flight.
-  constexpr int ROWS_EARLY = (WAVES == 4 && !COMPACT) ? 16 : 0;
-  using AllButRows = std::integral_constant<int, ROWS_EARLY>;
+  using AllButRows = std::integral_constant<int, WAVES == 4 ? 16 : 0>;
   using Everything = std::integral_constant<int, 0>;
   request_weights();
   // (Measured and not kept, config 2, against 10.5 us: the first tile's edge data by volatile-asm loads awaited by hand
@@ -248,9 +246,8 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 4 && COMPACT) ? 2 : 1) void c
 
     // ---- sender rows of this tile (one 16-B read per lane and edge: a half wave reads one whole 512-B row).  With
     //      one wave per SIMD they are requested first and consumed after GEMM2; with two waves per SIMD (WAVES = 8,
-    //      256 registers per wave) they are requested only after GEMM2 - the sibling wave's MFMAs cover the latency; the
-    //      256-register 4-wave build requests them right before GEMM2. ----
-    constexpr int X_AT = WAVES > 4 ? 2 : (COMPACT ? 1 : 0);  // 0: tile start, 1: before GEMM2, 2: after GEMM2
+    //      256 registers per wave) they are requested only after GEMM2 - the sibling wave's MFMAs cover the latency. ----
+    constexpr bool X_LATE = WAVES > 4;
     float xv[4][16];
     auto load_sender_rows = [&]() {
 #pragma unroll
@@ -265,7 +262,7 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 4 && COMPACT) ? 2 : 1) void c
         xv[3][r] = t.w;
       }
     };
-    if constexpr (X_AT == 0) load_sender_rows();
+    if constexpr (!X_LATE) load_sender_rows();
     prefetch_tile(tile0 + tile_step);  // next tile's edge data, in flight during this tile's GEMMs
 
     // ---- B operand of GEMM1: this lane's half of its edge's basis row (+ the constant 1 of the bias row) ----
@@ -526,7 +523,6 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 4 && COMPACT) ? 2 : 1) void c
       for (int i = 0; i < 8; ++i) split_into(0, i, a_hi, a_mid, a_lo);
     }
 
-    if constexpr (X_AT == 1) load_sender_rows();
     MP_STAMP(3)
     // ---- GEMM2: w[e][j] = sum_f h[e][f] W2[f][j] + b2[j]; A = the accumulator registers of GEMM1, split into three
     //      bf16 pieces per k block (16 features: 8 registers of each lane half); B = the pre-split images in LDS, one
@@ -645,7 +641,7 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 4 && COMPACT) ? 2 : 1) void c
 #undef MP_STEP_FENCE
 
     MP_STAMP(4)
-    if constexpr (X_AT == 2) load_sender_rows();
+    if constexpr (X_LATE) load_sender_rows();
     // ---- multiply by the sender row and sum the segments IN REGISTERS.  Each lane half holds 16 consecutive edges
     //      (register order) of the lane's four feature columns.  The segment structure is wave-uniform data (one
     //      32-bit start mask from a ballot), so the walk is driven by SCALAR tests: a step without a boundary in either
@@ -791,14 +787,7 @@ __global__ void cfconv_pack_kernel(const float* __restrict__ W1, const float* __
       for (int e = 0; e < 2; ++e) {
         const int ii = 2 * q + e;
         const int f = 32 * (m >> 1) + rowmap(8 * (m & 1) + ii, hh);
-        const float x = W2[f * F + 4 * cc + jb];
-        const __bf16 p0 = static_cast<__bf16>(x);
-        const float r1 = x - static_cast<float>(p0);
-        const __bf16 p1 = static_cast<__bf16>(r1);
-        const float r2 = r1 - static_cast<float>(p1);
-        const __bf16 p2 = static_cast<__bf16>(r2);
-        const __bf16 pick = piece == 0 ? p0 : (piece == 1 ? p1 : p2);
-        bits[e] = static_cast<unsigned>(__builtin_bit_cast(unsigned short, pick));
+        bits[e] = mp_bf16_piece_bits(W2[f * F + 4 * cc + jb], piece);
       }
       v = __uint_as_float(bits[0] | (bits[1] << 16));
     } else if (i < MAX_KROWS * F + W2_IMG_FLOATS + F) {
@@ -818,13 +807,7 @@ __global__ void cfconv_pack_kernel(const float* __restrict__ W1, const float* __
           float x = 0.0f;
           if (k < B) x = W1[k * F + 32 * ib + cc];
           else if (k == B && b1) x = b1[32 * ib + cc];
-          const __bf16 p0 = static_cast<__bf16>(x);
-          const float r1 = x - static_cast<float>(p0);
-          const __bf16 p1 = static_cast<__bf16>(r1);
-          const float r2 = r1 - static_cast<float>(p1);
-          const __bf16 p2 = static_cast<__bf16>(r2);
-          const __bf16 pick = piece == 0 ? p0 : (piece == 1 ? p1 : p2);
-          bits[e2] = static_cast<unsigned>(__builtin_bit_cast(unsigned short, pick));
+          bits[e2] = mp_bf16_piece_bits(x, piece);
         }
       }
       v = __uint_as_float(bits[0] | (bits[1] << 16));
@@ -864,39 +847,26 @@ __global__ void cfconv_boundary_kernel(const float* __restrict__ bnd_val, const 
   }
 }
 
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) is per device and per kernel: remember, under a mutex, on which
-// devices each instantiation has been opted in (a process may drive several GPUs, from several threads).
-inline int ensure_dynamic_lds(const void* kernel, size_t lds, unsigned long long* done_mask, std::mutex* mu) {
-  int dev = 0;
-  MP_HIP(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lock(*mu);
-  if (dev < 64 && ((*done_mask >> dev) & 1ull)) return MP_OK;
-  MP_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-  if (dev < 64) *done_mask |= 1ull << dev;
-  return MP_OK;
-}
-
 template <int WAVES, int NKT>
 size_t cfconv_lds_bytes() {
   const int w1 = (NKT > 0 && NKT <= G1B_MAX_NK) ? W1B_FLOATS : (NKT > 0 ? 2 * NKT : MAX_KROWS) * F;
   return sizeof(float) * (w1 + W2_IMG_FLOATS + WAVES * 2 * F);
 }
 
-template <int WAVES, bool GAUSS, bool FAST, int NKT, bool DIAG, bool COMPACT = false>
+template <int WAVES, bool GAUSS, bool FAST, int NKT, bool DIAG>
 int launch_cfconv(const CfconvArgs& args, int grid, hipStream_t s) {
   const size_t lds = cfconv_lds_bytes<WAVES, NKT>();
   static std::mutex mu;                    // one per instantiation, like the mask: guarded, per device
   static unsigned long long done_mask = 0;
-  const int rc = ensure_dynamic_lds(
-      reinterpret_cast<const void*>(&cfconv_fused_kernel<WAVES, GAUSS, FAST, NKT, DIAG, COMPACT>), lds, &done_mask, &mu);
+  const int rc = mp::ensure_dynamic_lds(reinterpret_cast<const void*>(&cfconv_fused_kernel<WAVES, GAUSS, FAST, NKT, DIAG>),
+                                        lds, &done_mask, &mu);
   if (rc != MP_OK) return rc;
-  cfconv_fused_kernel<WAVES, GAUSS, FAST, NKT, DIAG, COMPACT><<<grid, WAVES * 64, lds, s>>>(args);
+  cfconv_fused_kernel<WAVES, GAUSS, FAST, NKT, DIAG><<<grid, WAVES * 64, lds, s>>>(args);
   return mp::check_launch("mp_cfconv_fused_f32");
 }
 
 template <bool GAUSS, bool FAST>
-int launch_by_basis(const CfconvArgs& args, int waves, int grid, bool compact, hipStream_t s) {
-  (void)compact;   // flag bit 4 selects the 8-wave build in cfconv_dispatch (two waves per SIMD on ONE LDS image)
+int launch_by_basis(const CfconvArgs& args, int waves, int grid, hipStream_t s) {
   // basis sizes with a compile-time k count run GEMM1 on the bf16 pipe: 20 (SchNet default) and 25 (the fork's
   // force_schnet.py configuration); everything else takes the generic FP32 GEMM1
   // the 8-wave build (256 registers per wave) exists for the fast-softplus, fixed-basis builds only: with the exact
@@ -924,8 +894,8 @@ int cfconv_dispatch(CfconvArgs args, bool gauss, int flags, hipStream_t s) {
   // SIMD's lanes, so a single wave per SIMD leaves the matrix pipe idle during its own vector phases (softplus,
   // segment walk); a second wave per SIMD fills those gaps once the waves run out of step, i.e. when every wave has
   // several tiles: 8 waves (256 registers each, sender rows loaded late) from 4096 tiles on - measured 812 vs 928 us at
-  // 2.5 M edges, 87 vs 93 us at 0.2 M - and 4 waves (one tile per wave spread over more CUs) below.  Flag bit 2 forces
-  // 8 waves, bit 3 forces 4, bit 4 selects the 256-register 4-wave build (Gauss variant, 20 bins).
+  // 2.5 M edges, 87 vs 93 us at 0.2 M - and 4 waves (one tile per wave spread over more CUs) below.  Flag bit 2 (value 4)
+  // forces 8 waves, bit 3 (value 8) forces 4.
   // Between the regimes the launch is a whole number of ROUNDS over the resident waves (256 workgroups: 1024 waves of the
   // 4-wave build, 2048 of the 8-wave one), and a round of the 8-wave build - two waves sharing a SIMD - costs 1.85 rounds
   // of the 4-wave build (4093 tiles, a launch group of five config-2 batches: 4 rounds x 8.35 us against 2 x 15.45 us;
@@ -939,13 +909,14 @@ int cfconv_dispatch(CfconvArgs args, bool gauss, int flags, hipStream_t s) {
   if (flags & 4) waves = 8;
   if (flags & 8) waves = 4;
   if (!(fast && (args.B == 20 || args.B == 25))) waves = 4;   // no spill-free 8-wave build for these (launch_by_basis)
-  // Flag bit 4 ("several forwards in flight"): every workgroup claims a whole CU (all its registers, 107-120 KB of LDS), so
-  // forwards of different batches share the GPU only CU by CU; with this flag a launch uses half as many workgroups, two
-  // tiles per wave - the per-workgroup fixed cost (launch ramp, 107 KB of weight staging) is paid once per eight tiles
-  // and the other half of the CUs is free for the other batches' kernels.  Costs a lone launch latency; not the default.
-  const bool compact = (flags & 16) != 0;
+  // Flag bit 4 (value 16, "several forwards in flight"): every workgroup claims a whole CU (all its registers, 107-120 KB
+  // of LDS), so forwards of different batches share the GPU only CU by CU; with this flag a launch uses half as many
+  // workgroups, two tiles per wave - the per-workgroup fixed cost (launch ramp, 107 KB of weight staging) is paid once per
+  // eight tiles and the other half of the CUs is free for the other batches' kernels.  Costs a lone launch latency; not
+  // the default.
+  const bool half_grid = (flags & 16) != 0;
   int grid = (args.ntiles + waves - 1) / waves;
-  if (compact && grid > 1) grid = (grid + 1) / 2;
+  if (half_grid && grid > 1) grid = (grid + 1) / 2;
   if (grid > 256) grid = 256;
   if (args.diag) {
     MP_REQUIRE(gauss && args.B == 20, "mp_cfconv: the diagnostic build exists for the 20-bin Gauss variant only");
@@ -956,11 +927,9 @@ int cfconv_dispatch(CfconvArgs args, bool gauss, int flags, hipStream_t s) {
     MP_HIP(hipMemsetAsync(args.bnd_node, 0xff, sizeof(int32_t) * 2 * static_cast<size_t>(args.ntiles), s));
   int rc;
   if (gauss) {
-    rc = fast ? launch_by_basis<true, true>(args, waves, grid, compact, s)
-              : launch_by_basis<true, false>(args, waves, grid, compact, s);
+    rc = fast ? launch_by_basis<true, true>(args, waves, grid, s) : launch_by_basis<true, false>(args, waves, grid, s);
   } else {
-    rc = fast ? launch_by_basis<false, true>(args, waves, grid, compact, s)
-              : launch_by_basis<false, false>(args, waves, grid, compact, s);
+    rc = fast ? launch_by_basis<false, true>(args, waves, grid, s) : launch_by_basis<false, false>(args, waves, grid, s);
   }
   if (rc != MP_OK || args.bnd_val == nullptr) return rc;
   const int64_t nslots = 2 * static_cast<int64_t>(args.ntiles);
@@ -983,6 +952,20 @@ int attach_det_workspace(CfconvArgs* a, int flags, void* ws, size_t ws_bytes, co
   return MP_OK;
 }
 
+// The argument block of every entry point; the Gauss ones pass the basis parameters (sigma != 0 is their own check).
+CfconvArgs make_args(const float* x, int64_t N, const float* edge_in, int B, const float* packed, const int32_t* recv,
+                     const int32_t* send, const int32_t* perm, int64_t M, float* out, float distance = 0.0f,
+                     float sigma = 0.0f, float offset = 0.0f) {
+  CfconvArgs a{};
+  a.x = x; a.edge_in = edge_in; a.packed = packed;
+  a.recv = recv; a.send = send; a.perm = perm; a.out = out;
+  a.M = M; a.N = N; a.B = B;
+  a.g_distance = distance;
+  if (sigma != 0.0f) a.g_gamma = static_cast<float>(1.0 / static_cast<double>(sigma) / static_cast<double>(sigma) / 2.0);
+  a.g_offset = offset;
+  return a;
+}
+
 }  // namespace
 
 extern "C" {
@@ -997,28 +980,20 @@ int mp_cfconv_pack_f32(const float* W1, const float* b1, int B, const float* W2,
   return mp::check_launch("mp_cfconv_pack_f32");
 }
 
+// Flag bit 5 (deterministic) needs the workspace of the _ws_ entry points; the two without one ignore it.
 int mp_cfconv_fused_f32(const float* x, int64_t N, const float* rbf, int B, const float* packed,
                         const int32_t* recv_sorted, const int32_t* send, const int32_t* perm, int64_t M, int flags,
                         float* out_zeroed, mpStream_t stream) {
-  CfconvArgs a{};
-  a.x = x; a.edge_in = rbf; a.packed = packed;
-  a.recv = recv_sorted; a.send = send; a.perm = perm; a.out = out_zeroed;
-  a.M = M; a.N = N; a.B = B;
-  return cfconv_dispatch(a, false, flags, mp::as_stream(stream));
+  return mp_cfconv_fused_ws_f32(x, N, rbf, B, packed, recv_sorted, send, perm, M, flags & ~32, out_zeroed, nullptr, 0,
+                                stream);
 }
 
 int mp_cfconv_gauss_fused_f32(const float* x, int64_t N, const float* dist, int bins, float distance, float sigma,
                               float offset, const float* packed, const int32_t* recv_sorted, const int32_t* send,
                               const int32_t* perm, int64_t M, int flags, float* out_zeroed, mpStream_t stream) {
   MP_REQUIRE(sigma != 0.0f, "mp_cfconv_gauss_fused_f32: sigma must be non-zero");
-  CfconvArgs a{};
-  a.x = x; a.edge_in = dist; a.packed = packed;
-  a.recv = recv_sorted; a.send = send; a.perm = perm; a.out = out_zeroed;
-  a.M = M; a.N = N; a.B = bins;
-  a.g_distance = distance;
-  a.g_gamma = static_cast<float>(1.0 / static_cast<double>(sigma) / static_cast<double>(sigma) / 2.0);
-  a.g_offset = offset;
-  return cfconv_dispatch(a, true, flags, mp::as_stream(stream));
+  return mp_cfconv_gauss_fused_ws_f32(x, N, dist, bins, distance, sigma, offset, packed, recv_sorted, send, perm, M,
+                                      flags & ~32, out_zeroed, nullptr, 0, stream);
 }
 
 int mp_cfconv_det_workspace_bytes(int64_t M, size_t* bytes_out_host) {
@@ -1030,10 +1005,7 @@ int mp_cfconv_det_workspace_bytes(int64_t M, size_t* bytes_out_host) {
 int mp_cfconv_fused_ws_f32(const float* x, int64_t N, const float* rbf, int B, const float* packed,
                            const int32_t* recv_sorted, const int32_t* send, const int32_t* perm, int64_t M, int flags,
                            float* out_zeroed, void* ws, size_t ws_bytes, mpStream_t stream) {
-  CfconvArgs a{};
-  a.x = x; a.edge_in = rbf; a.packed = packed;
-  a.recv = recv_sorted; a.send = send; a.perm = perm; a.out = out_zeroed;
-  a.M = M; a.N = N; a.B = B;
+  CfconvArgs a = make_args(x, N, rbf, B, packed, recv_sorted, send, perm, M, out_zeroed);
   const int rc = attach_det_workspace(&a, flags, ws, ws_bytes, "mp_cfconv_fused_ws_f32");
   if (rc != MP_OK) return rc;
   return cfconv_dispatch(a, false, flags, mp::as_stream(stream));
@@ -1044,13 +1016,7 @@ int mp_cfconv_gauss_fused_ws_f32(const float* x, int64_t N, const float* dist, i
                                  const int32_t* perm, int64_t M, int flags, float* out_zeroed, void* ws, size_t ws_bytes,
                                  mpStream_t stream) {
   MP_REQUIRE(sigma != 0.0f, "mp_cfconv_gauss_fused_ws_f32: sigma must be non-zero");
-  CfconvArgs a{};
-  a.x = x; a.edge_in = dist; a.packed = packed;
-  a.recv = recv_sorted; a.send = send; a.perm = perm; a.out = out_zeroed;
-  a.M = M; a.N = N; a.B = bins;
-  a.g_distance = distance;
-  a.g_gamma = static_cast<float>(1.0 / static_cast<double>(sigma) / static_cast<double>(sigma) / 2.0);
-  a.g_offset = offset;
+  CfconvArgs a = make_args(x, N, dist, bins, packed, recv_sorted, send, perm, M, out_zeroed, distance, sigma, offset);
   const int rc = attach_det_workspace(&a, flags, ws, ws_bytes, "mp_cfconv_gauss_fused_ws_f32");
   if (rc != MP_OK) return rc;
   return cfconv_dispatch(a, true, flags, mp::as_stream(stream));
@@ -1064,13 +1030,7 @@ int mp_cfconv_gauss_diag_f32(const float* x, int64_t N, const float* dist, int b
                              const int32_t* perm, int64_t M, float* out_zeroed, unsigned long long* diag8,
                              mpStream_t stream) {
   MP_REQUIRE(sigma != 0.0f && diag8, "mp_cfconv_gauss_diag_f32: bad arguments");
-  CfconvArgs a{};
-  a.x = x; a.edge_in = dist; a.packed = packed;
-  a.recv = recv_sorted; a.send = send; a.perm = perm; a.out = out_zeroed;
-  a.M = M; a.N = N; a.B = bins;
-  a.g_distance = distance;
-  a.g_gamma = static_cast<float>(1.0 / static_cast<double>(sigma) / static_cast<double>(sigma) / 2.0);
-  a.g_offset = offset;
+  CfconvArgs a = make_args(x, N, dist, bins, packed, recv_sorted, send, perm, M, out_zeroed, distance, sigma, offset);
   a.diag = diag8;
   return cfconv_dispatch(a, true, 1, mp::as_stream(stream));
 }

@@ -21,7 +21,6 @@
 // cycles, pinned to MFMA slots (a bf16 MFMA leaves 24 of its 32 cycles to the vector unit): the splits of v and the
 // sigmoid of P ride under GH's MFMAs.  LDS per workgroup: W1 as bf16 pieces (24 KB) and as FP32 rows (17 KB, large
 // bases) + the three W2 images = 137 KB, staged by LDS-DMA.
-#include <mutex>
 
 #include "mp_common.h"
 
@@ -375,13 +374,7 @@ __global__ void cfconv_bwd_pack_kernel(const float* __restrict__ W1, const float
           float x = 0.0f;
           if (k < B) x = W1[k * F + 32 * ib + cc];
           else if (k == B && b1) x = b1[32 * ib + cc];
-          const __bf16 p0 = static_cast<__bf16>(x);
-          const float r1 = x - static_cast<float>(p0);
-          const __bf16 p1 = static_cast<__bf16>(r1);
-          const float r2 = r1 - static_cast<float>(p1);
-          const __bf16 p2 = static_cast<__bf16>(r2);
-          const __bf16 pick = piece == 0 ? p0 : (piece == 1 ? p1 : p2);
-          bits[e2] = static_cast<unsigned>(__builtin_bit_cast(unsigned short, pick));
+          bits[e2] = mp_bf16_piece_bits(x, piece);
         }
       }
       v = __uint_as_float(bits[0] | (bits[1] << 16));
@@ -391,17 +384,9 @@ __global__ void cfconv_bwd_pack_kernel(const float* __restrict__ W1, const float
       const int q = t & 3, ln = (t >> 2) & 63, ib = (t >> 8) & 3, kb = t >> 10;
       const int hl = ln & 31, kh = ln >> 5;
       unsigned bits[2];
-      for (int e = 0; e < 2; ++e) {
-        const float x = W2[(32 * ib + hl) * F + 16 * kb + 8 * kh + 2 * q + e];
-        const __bf16 p0 = static_cast<__bf16>(x);
-        const float r1 = x - static_cast<float>(p0);
-        const __bf16 p1 = static_cast<__bf16>(r1);
-        const float r2 = r1 - static_cast<float>(p1);
-        const __bf16 p2 = static_cast<__bf16>(r2);
-        const __bf16 pick = piece == 0 ? p0 : (piece == 1 ? p1 : p2);
-        bits[e] = static_cast<unsigned>(__builtin_bit_cast(unsigned short, pick));
-      }
-      v = __uint_as_float(bits[0] | (bits[1] << 16));
+      for (int e = 0; e < 2; ++e)
+        bits[e] = mp_bf16_piece_bits(W2[(32 * ib + hl) * F + 16 * kb + 8 * kh + 2 * q + e], piece);
+      v =__uint_as_float(bits[0] | (bits[1] << 16));
     }
     packed[i] = v;
   }
@@ -439,17 +424,10 @@ int mp_cfconv_gauss_dist_grad_f32(const float* x, const float* g_out, int64_t N,
   const bool g1b = ((bins + 2) >> 1) <= G1B_MAX_NK;
   static std::mutex mu;                      // dynamic-LDS opt-in: per device (and build), guarded
   static unsigned long long done_mask[2] = {0, 0};
-  {
-    int dev = 0;
-    MP_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(mu);
-    if (dev >= 64 || !((done_mask[g1b] >> dev) & 1ull)) {
-      const void* fn = g1b ? reinterpret_cast<const void*>(&cfconv_dist_grad_kernel<true>)
-                           : reinterpret_cast<const void*>(&cfconv_dist_grad_kernel<false>);
-      MP_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-      if (dev < 64) done_mask[g1b] |= 1ull << dev;
-    }
-  }
+  const void* fn = g1b ? reinterpret_cast<const void*>(&cfconv_dist_grad_kernel<true>)
+                       : reinterpret_cast<const void*>(&cfconv_dist_grad_kernel<false>);
+  const int rc = mp::ensure_dynamic_lds(fn, lds, &done_mask[g1b], &mu);
+  if (rc != MP_OK) return rc;
   int grid = (a.ntiles + WAVES - 1) / WAVES;
   if (grid > 256) grid = 256;
   if (g1b) cfconv_dist_grad_kernel<true><<<grid, WAVES * 64, lds, mp::as_stream(stream)>>>(a);

@@ -13,7 +13,6 @@
 //   stage 2:  out = m W2 + b2 + addend                              (absent: out = stage 1 + addend, any U1)
 //
 // W1 / W2 are mp_chain_pack_f32 images: the k-major register order of one wave's column slice, 16-B loads.
-#include <mutex>
 
 #include "mp_common.h"
 
@@ -609,16 +608,8 @@ int mp_painn_update_fused_f32(const float* z, const float* v, const float* uv, i
   const size_t lds = sizeof(float) * UPD_LDS_FLOATS;
   static std::mutex mu;                      // dynamic-LDS opt-in: per device, guarded
   static unsigned long long done_mask = 0;
-  {
-    int dev = 0;
-    MP_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(mu);
-    if (dev >= 64 || !((done_mask >> dev) & 1ull)) {
-      MP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&painn_update_chain_kernel),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-      if (dev < 64) done_mask |= 1ull << dev;
-    }
-  }
+  const int rc = mp::ensure_dynamic_lds(reinterpret_cast<const void*>(&painn_update_chain_kernel), lds, &done_mask, &mu);
+  if (rc != MP_OK) return rc;
   const int grid = a.ntiles < 256 ? a.ntiles : 256;
   painn_update_chain_kernel<<<grid, 512, lds, mp::as_stream(stream)>>>(a);
   return mp::check_launch("mp_painn_update_fused_f32");
@@ -640,16 +631,9 @@ int mp_painn_update_fused_bwd_f32(const float* g_z2, const float* g_v2, const fl
   const size_t lds = sizeof(float) * UB_LDS_FLOATS;
   static std::mutex mu;                      // dynamic-LDS opt-in: per device, guarded
   static unsigned long long done_mask = 0;
-  {
-    int dev = 0;
-    MP_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(mu);
-    if (dev >= 64 || !((done_mask >> dev) & 1ull)) {
-      MP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&painn_update_bwd_chain_kernel),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-      if (dev < 64) done_mask |= 1ull << dev;
-    }
-  }
+  const int rc =
+      mp::ensure_dynamic_lds(reinterpret_cast<const void*>(&painn_update_bwd_chain_kernel), lds, &done_mask, &mu);
+  if (rc != MP_OK) return rc;
   const int grid = q.ntiles < 256 ? q.ntiles : 256;
   painn_update_bwd_chain_kernel<<<grid, 512, lds, mp::as_stream(stream)>>>(q);
   return mp::check_launch("mp_painn_update_fused_bwd_f32");

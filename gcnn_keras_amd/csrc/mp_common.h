@@ -5,6 +5,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <mutex>
 
 #include "../../include/mpengine.h"
 
@@ -56,6 +57,23 @@ inline unsigned grid_for(int64_t work_items, int block = 256) {
     }                                                                         \
   } while (0)
 
+namespace mp {
+
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize) is per device and per kernel: remember, under a mutex, on which
+// devices a kernel has been opted in (a process may drive several GPUs, from several threads).  The caller keeps one
+// static mask / mutex pair per kernel instantiation.
+inline int ensure_dynamic_lds(const void* kernel, size_t bytes, unsigned long long* done_mask, std::mutex* mu) {
+  int dev = 0;
+  MP_HIP(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> lock(*mu);
+  if (dev < 64 && ((*done_mask >> dev) & 1ull)) return MP_OK;
+  MP_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes)));
+  if (dev < 64) *done_mask |= 1ull << dev;
+  return MP_OK;
+}
+
+}  // namespace mp
+
 // Activation functors shared by the dense epilogue and the standalone activation kernel.
 // shifted_softplus restates kgcnn/ops/activ.py:15 with TF's thresholded softplus
 // (x > -thr -> x ; x < thr -> exp(x) ; else log1p(exp(x)), thr = log(eps_f32) + 2).
@@ -91,6 +109,19 @@ __device__ __forceinline__ int64_t mp_owner_of(const int64_t* __restrict__ split
     if (splits[mid] <= e) lo = mid; else hi = mid;
   }
   return lo;
+}
+
+// Piece `piece` (0 = hi, 1 = mid, 2 = lo) of the exact three-way bf16 split of x, as bf16 bits: hi = bf16(x),
+// mid = bf16(x - hi), lo = bf16(x - hi - mid), each difference exact in FP32.  For the weight-pack kernels (once per
+// weight update); the hot kernels split in registers.
+__device__ __forceinline__ unsigned mp_bf16_piece_bits(float x, int piece) {
+  const __bf16 p0 = static_cast<__bf16>(x);
+  const float r1 = x - static_cast<float>(p0);
+  const __bf16 p1 = static_cast<__bf16>(r1);
+  const float r2 = r1 - static_cast<float>(p1);
+  const __bf16 p2 = static_cast<__bf16>(r2);
+  const __bf16 pick = piece == 0 ? p0 : (piece == 1 ? p1 : p2);
+  return static_cast<unsigned>(__builtin_bit_cast(unsigned short, pick));
 }
 
 // x^n by repeated multiplication, n >= 0 (the polynomial envelopes: n is a small layer constant)

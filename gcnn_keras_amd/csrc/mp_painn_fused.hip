@@ -20,7 +20,6 @@
 // All kernels are HBM/L2-bound streaming or gather kernels except the GEMMs.  The per-edge filter (K = B = 20) runs on the
 // VALU as packed FP32 FMAs with the lane's weight columns in registers in the gather kernels, and on the matrix pipe
 // (bf16x3) in the LDS tile kernels.
-#include <mutex>
 
 #include "mp_common.h"
 #include "mp_edge_prepare.h"
@@ -1449,18 +1448,9 @@ int mp_painn_message_tiles_f32(const float* s, const float* v, int64_t N, const 
   auto launch = [&](auto kernel) -> int {
     static std::mutex mu;
     static unsigned long long done = 0;       // one static pair per instantiation of this lambda's call operator
-    int dev = 0;
-    MP_HIP(hipGetDevice(&dev));
-    {
-      std::lock_guard<std::mutex> lock(mu);
-      if (dev >= 64 || !((done >> dev) & 1ull)) {
-        MP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   160 * 1024));
-        if (dev < 64) done |= 1ull << dev;
-      }
-    }
-    kernel<<<blocks, 256, lds, st>>>(a);
-    return MP_OK;
+    const int rc = mp::ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), 160 * 1024, &done, &mu);
+    if (rc == MP_OK) kernel<<<blocks, 256, lds, st>>>(a);
+    return rc;
   };
   int lr;
   if (B == 20) lr = env ? launch(painn_message_tile_kernel<20, true>) : launch(painn_message_tile_kernel<20, false>);
@@ -1503,18 +1493,9 @@ int mp_painn_message_bwd_tiles_f32(const float* s, const float* v, int64_t N, co
   auto launch = [&](auto kernel) -> int {
     static std::mutex mu;
     static unsigned long long done = 0;       // one static pair per instantiation of this lambda's call operator
-    int dev = 0;
-    MP_HIP(hipGetDevice(&dev));
-    {
-      std::lock_guard<std::mutex> lock(mu);
-      if (dev >= 64 || !((done >> dev) & 1ull)) {
-        MP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   160 * 1024));
-        if (dev < 64) done |= 1ull << dev;
-      }
-    }
-    kernel<<<blocks, 256, lds, st>>>(a);
-    return MP_OK;
+    const int rc = mp::ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), 160 * 1024, &done, &mu);
+    if (rc == MP_OK) kernel<<<blocks, 256, lds, st>>>(a);
+    return rc;
   };
   int lr;
   if (B == 20) lr = env ? launch(painn_message_bwd_tile_kernel<20, true>) : launch(painn_message_bwd_tile_kernel<20, false>);

@@ -423,13 +423,14 @@ __global__ __launch_bounds__(BF ? 512 : 256, (MODE != NODE_LAST && !SAVE && !BF)
 // Stage 0 of the fused forward: the node-input chain (Embedding -> Dense -> Dense_nobias) and the edge preparation
 // (index shift, receiver/sender split, flags, distance) are independent, and at QM9 batch sizes each alone fills less
 // than half of the chip for ~5 us - so one launch runs both, on disjoint workgroups (role by block index).
-template <int E, bool FAST, bool LDS_SPLITS, bool PACKED, bool BF = false>
+// Packed weight images only (FP32, or bf16 pieces with BF); the row splits of the edge preparation are staged in LDS.
+template <int E, bool FAST, bool BF = false>
 __global__ __launch_bounds__(BF ? 512 : 256) void schnet_stage0_kernel(NodeArgs a, mp_prep::EdgePrepArgs p, int node_blocks) {
   if (static_cast<int>(blockIdx.x) < node_blocks) {
-    schnet_node_body<NODE_IN, E, 1, FAST, PACKED, false, BF>(a, blockIdx.x, node_blocks);
+    schnet_node_body<NODE_IN, E, 1, FAST, true, false, BF>(a, blockIdx.x, node_blocks);
   } else {
-    mp_prep::edge_prepare_body<LDS_SPLITS>(p, static_cast<int64_t>(blockIdx.x) - node_blocks,
-                                           static_cast<int64_t>(gridDim.x) - node_blocks);
+    mp_prep::edge_prepare_body<true>(p, static_cast<int64_t>(blockIdx.x) - node_blocks,
+                                     static_cast<int64_t>(gridDim.x) - node_blocks);
   }
 }
 
@@ -592,60 +593,50 @@ __global__ void node_pack_bf16_kernel(const float* __restrict__ W, int K, int U,
     unsigned bits[2];
     for (int e = 0; e < 2; ++e) {
       const int k = 32 * kb + 8 * (lane >> 4) + 2 * d + e;
-      const float x = W[k * U + col];
-      const __bf16 p0 = static_cast<__bf16>(x);
-      const float r1 = x - static_cast<float>(p0);
-      const __bf16 p1 = static_cast<__bf16>(r1);
-      const float r2 = r1 - static_cast<float>(p1);
-      const __bf16 p2 = static_cast<__bf16>(r2);
-      const __bf16 pick = pc == 0 ? p0 : (pc == 1 ? p1 : p2);
-      bits[e] = static_cast<unsigned>(__builtin_bit_cast(unsigned short, pick));
+      bits[e] = mp_bf16_piece_bits(W[k * U + col], pc);
     }
     packed[i] = __uint_as_float(bits[0] | (bits[1] << 16));
   }
 }
 
+// NODE_UPD (the layer path) reads raw Keras kernels; the other modes read packed images only - their entry points
+// require flags bit 1, checked before any device work.
 template <int MODE, int E>
 int launch_node(const NodeArgs& a, int flags, hipStream_t s, const char* what) {
-  if constexpr (MODE == NODE_MID || MODE == NODE_LAST) {   // the energy + force pass: packed images only
-    if (a.save_d2)
-      return (flags & 1) ? launch_node_impl<MODE, E, true, true, true>(a, s, what, flags)
-                         : launch_node_impl<MODE, E, false, true, true>(a, s, what, flags);
-  }
-  if constexpr (MODE != NODE_UPD) {   // flags bit 6 (with bit 1): mp_schnet_node_pack_bf16_f32 images, bf16-pipe GEMMs
-    if ((flags & 66) == 66)
+  if constexpr (MODE == NODE_UPD) {
+    return (flags & 1) ? launch_node_impl<MODE, E, true, false>(a, s, what, flags)
+                       : launch_node_impl<MODE, E, false, false>(a, s, what, flags);
+  } else {
+    if constexpr (MODE == NODE_MID || MODE == NODE_LAST) {   // the energy + force pass
+      if (a.save_d2)
+        return (flags & 1) ? launch_node_impl<MODE, E, true, true, true>(a, s, what, flags)
+                           : launch_node_impl<MODE, E, false, true, true>(a, s, what, flags);
+    }
+    if (flags & 64)   // mp_schnet_node_pack_bf16_f32 images, bf16-pipe GEMMs
       return (flags & 1) ? launch_node_impl<MODE, E, true, true, false, true>(a, s, what, flags)
                          : launch_node_impl<MODE, E, false, true, false, true>(a, s, what, flags);
+    return (flags & 1) ? launch_node_impl<MODE, E, true, true>(a, s, what, flags)   // mp_schnet_node_pack_f32 images
+                       : launch_node_impl<MODE, E, false, true>(a, s, what, flags);
   }
-  if constexpr (MODE != NODE_UPD) {   // flags bit 1: the weight pointers are mp_schnet_node_pack_f32 images
-    if (flags & 2)
-      return (flags & 1) ? launch_node_impl<MODE, E, true, true>(a, s, what, flags)
-                         : launch_node_impl<MODE, E, false, true>(a, s, what, flags);
-  }
-  return (flags & 1) ? launch_node_impl<MODE, E, true, false>(a, s, what, flags)
-                     : launch_node_impl<MODE, E, false, false>(a, s, what, flags);
 }
 
 template <int E>
 void launch_stage0(const NodeArgs& a, const mp_prep::EdgePrepArgs& p, int node_blocks, unsigned grid, int flags_arg,
                    hipStream_t s) {
-  if ((flags_arg & 66) == 66) {   // bf16-piece weight images
+  if (flags_arg & 64) {   // bf16-piece weight images
     // (eight-wave node workgroups; the edge-preparation workgroups of the launch are block-size agnostic: half as many)
     // at most 64 of them: every edge workgroup first stages both row-split arrays in LDS (10 KB at 640 graphs), which is
     // most of what a workgroup with 512 edges does - a launch group's 131 k edges on 64 workgroups (four edges per thread)
-    // instead of 256: +2 % in flight (scripts/probes/ab_stage0_edge_cap.sh); a lone 128-graph batch has 51 anyway
+    // instead of 256: +2 % in flight; a lone 128-graph batch has 51 anyway
     unsigned eblocks = (grid - static_cast<unsigned>(node_blocks) + 1) / 2;
     if (eblocks > 64) eblocks = 64;
     const unsigned grid8 = static_cast<unsigned>(node_blocks) + eblocks;
-    if (flags_arg & 1) schnet_stage0_kernel<E, true, true, true, true><<<grid8, 512, 0, s>>>(a, p, node_blocks);
-    else schnet_stage0_kernel<E, false, true, true, true><<<grid8, 512, 0, s>>>(a, p, node_blocks);
-    return;
-  }
-  switch (flags_arg & 3) {
-    case 0: schnet_stage0_kernel<E, false, true, false><<<grid, 256, 0, s>>>(a, p, node_blocks); break;
-    case 1: schnet_stage0_kernel<E, true, true, false><<<grid, 256, 0, s>>>(a, p, node_blocks); break;
-    case 2: schnet_stage0_kernel<E, false, true, true><<<grid, 256, 0, s>>>(a, p, node_blocks); break;
-    default: schnet_stage0_kernel<E, true, true, true><<<grid, 256, 0, s>>>(a, p, node_blocks); break;
+    if (flags_arg & 1) schnet_stage0_kernel<E, true, true><<<grid8, 512, 0, s>>>(a, p, node_blocks);
+    else schnet_stage0_kernel<E, false, true><<<grid8, 512, 0, s>>>(a, p, node_blocks);
+  } else if (flags_arg & 1) {
+    schnet_stage0_kernel<E, true><<<grid, 256, 0, s>>>(a, p, node_blocks);
+  } else {
+    schnet_stage0_kernel<E, false><<<grid, 256, 0, s>>>(a, p, node_blocks);
   }
 }
 
@@ -665,6 +656,7 @@ int mp_debug_node_diag(unsigned long long* out8_host) {  // diagnostic build onl
 // flags bit 8 (value 256): `numbers` points to int64 node numbers instead of float32
 int mp_schnet_node_in_f32(const float* numbers, int64_t N, const float* emb, int vocab, int emb_dim, const float* W0,
                           const float* b0, const float* Wx, float* n_out, float* x_out, int flags, mpStream_t stream) {
+  MP_REQUIRE(flags & 2, "mp_schnet_node_in_f32: flags bit 1 is required (packed weight images only)");
   MP_REQUIRE(N >= 0 && vocab >= 1, "mp_schnet_node_in_f32: bad sizes");
   MP_REQUIRE(emb_dim == 64 || emb_dim == 128, "mp_schnet_node_in_f32: built for embedding width 64 or 128 (got %d)",
              emb_dim);
@@ -682,6 +674,7 @@ int mp_schnet_stage0_f32(const float* numbers, int64_t N, const float* emb, int 
                          const float* b0, const float* Wx, float* n_out, float* x_out, const int64_t* idx, int64_t M,
                          const int64_t* node_splits, const int64_t* edge_splits, int64_t G, const float* xyz,
                          int32_t* recv, int32_t* send, float* dist, int32_t* flags, int flags_arg, mpStream_t stream) {
+  MP_REQUIRE(flags_arg & 2, "mp_schnet_stage0_f32: flags bit 1 is required (packed weight images only)");
   MP_REQUIRE(N >= 0 && M >= 0 && G >= 0 && vocab >= 1, "mp_schnet_stage0_f32: bad sizes");
   MP_REQUIRE(emb_dim == 64 || emb_dim == 128, "mp_schnet_stage0_f32: built for embedding width 64 or 128 (got %d)",
              emb_dim);
@@ -704,7 +697,7 @@ int mp_schnet_stage0_f32(const float* numbers, int64_t N, const float* emb, int 
   // node chain: persistent over the tiles beyond one workgroup per CU (a workgroup's weight slices - 72 KB as bf16 pieces -
   // are loaded once for its tiles, not once per tile: launch groups of five batches have 720 tiles)
   // eight-wave bf16-piece build: one workgroup per CU; half the CUs with flag bit 9 (launch_node_impl)
-  const int node_cap = ((flags_arg & 66) == 66) ? (((flags_arg & 512) && a.ntiles >= 256) ? 128 : 256) : 512;
+  const int node_cap = (flags_arg & 64) ? (((flags_arg & 512) && a.ntiles >= 256) ? 128 : 256) : 512;
   const int node_blocks = a.ntiles < node_cap ? a.ntiles : node_cap;
   const int edge_blocks = static_cast<int>(mp::grid_for(M));
   hipStream_t s = mp::as_stream(stream);
@@ -717,10 +710,10 @@ int mp_schnet_stage0_f32(const float* numbers, int64_t N, const float* emb, int 
 int mp_schnet_node_update_save_f32(float* agg, int64_t N, const float* W2, const float* b2, const float* W3,
                                    const float* b3, float* n_inout, const float* Wx_next, float* x_out, float* d2_out,
                                    int flags, mpStream_t stream) {
+  MP_REQUIRE(flags & 2, "mp_schnet_node_update_f32: flags bit 1 is required (packed weight images only)");
   MP_REQUIRE(N >= 0, "mp_schnet_node_update_f32: bad sizes");
   if (N == 0) return MP_OK;
   MP_REQUIRE(agg && W2 && W3 && n_inout && Wx_next && x_out, "mp_schnet_node_update_f32: null pointer");
-  MP_REQUIRE(d2_out == nullptr || (flags & 2), "mp_schnet_node_update_save_f32: saving needs packed weight images");
   NodeArgs a{};
   a.N = N;
   a.agg = agg; a.W2 = W2; a.b2 = b2; a.W3 = W3; a.b3 = b3; a.n = n_inout; a.Wx = Wx_next; a.x = x_out;
@@ -766,12 +759,12 @@ int mp_schnet_node_last_save_f32(float* agg, int64_t N, const float* W2, const f
                                  const float* b3, const float* n_in, const float* Wl0, const float* bl0,
                                  const float* Wl1, const float* bl1, float* h_out, float* d2_out, float* dl0_out,
                                  float* dl1_out, int flags, mpStream_t stream) {
+  MP_REQUIRE(flags & 2, "mp_schnet_node_last_f32: flags bit 1 is required (packed weight images only)");
   MP_REQUIRE(N >= 0, "mp_schnet_node_last_f32: bad sizes");
   if (N == 0) return MP_OK;
   MP_REQUIRE(agg && W2 && W3 && n_in && Wl0 && Wl1 && h_out, "mp_schnet_node_last_f32: null pointer");
   MP_REQUIRE((d2_out == nullptr) == (dl0_out == nullptr) && (d2_out == nullptr) == (dl1_out == nullptr),
              "mp_schnet_node_last_save_f32: give all three derivative buffers or none");
-  MP_REQUIRE(d2_out == nullptr || (flags & 2), "mp_schnet_node_last_save_f32: saving needs packed weight images");
   NodeArgs a{};
   a.N = N;
   a.agg = agg; a.W2 = W2; a.b2 = b2; a.W3 = W3; a.b3 = b3; a.n = const_cast<float*>(n_in);

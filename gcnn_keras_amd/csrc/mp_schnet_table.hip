@@ -185,17 +185,16 @@ constexpr int NODES_PER_BLOCK = (256 / 64) * 2 * GU;   // one step of a 256-thre
 // Workgroup split of the one-launch stage 0.  Node role: one step per workgroup up to 512 of them (a union batch of
 // 11.5 k nodes: 360) - the role holds no per-workgroup state, so the chain's one-workgroup-per-CU cap and the
 // half-the-CUs rule of flag bit 9 (both there to amortise its weight slices) do not apply.  Edge role: one edge per thread
-// up to `edge_cap` workgroups; every edge workgroup first stages both row-split arrays in LDS, which is most of what a
+// up to EDGE_CAP workgroups; every edge workgroup first stages both row-split arrays in LDS, which is most of what a
 // workgroup with few edges does, hence the cap: 128 workgroups of 256 threads, the thread count of the chain build's cap
-// (64 of 512).  flags_arg bits 16-23, when set, give another cap in units of 16 workgroups (A/B runs).  `several`: the cap
-// bites, a thread has more than one edge (the build with four edges in flight per thread).
-void stage0_split(int64_t N, int64_t M, int flags_arg, int* node_blocks, unsigned* grid, bool* several) {
+// (64 of 512).  `several`: the cap bites, a thread has more than one edge (the build with four edges in flight per
+// thread).
+constexpr unsigned EDGE_CAP = 128;
+void stage0_split(int64_t N, int64_t M, int* node_blocks, unsigned* grid, bool* several) {
   const int64_t nb = mp::ceil_div(N, NODES_PER_BLOCK);
   *node_blocks = static_cast<int>(nb < 512 ? nb : 512);
-  const int knob = (flags_arg >> 16) & 255;
-  const unsigned edge_cap = knob ? 16u * static_cast<unsigned>(knob) : 128u;
   unsigned eb = mp::grid_for(M);
-  if (eb > edge_cap) eb = edge_cap;
+  if (eb > EDGE_CAP) eb = EDGE_CAP;
   *grid = static_cast<unsigned>(*node_blocks) + eb;
   *several = M > static_cast<int64_t>(eb) * 256;
 }
@@ -253,7 +252,7 @@ int mp_schnet_stage0_table_f32(const float* numbers, int64_t N, int vocab, const
   int node_blocks;
   unsigned grid;
   bool several;
-  stage0_split(N, M, flags_arg, &node_blocks, &grid, &several);
+  stage0_split(N, M, &node_blocks, &grid, &several);
   if (several) schnet_stage0_table_kernel<4><<<grid, 256, 0, mp::as_stream(stream)>>>(a, p, node_blocks);
   else schnet_stage0_table_kernel<1><<<grid, 256, 0, mp::as_stream(stream)>>>(a, p, node_blocks);
   return mp::check_launch("mp_schnet_stage0_table_f32");

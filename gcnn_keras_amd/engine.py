@@ -81,11 +81,9 @@ class SchnetForward:
         # device), `in_flight` such groups in flight on their own streams
         self.group = max(1, int(group)) if mode == "fused" else 1
         self._group_inputs = []
-        # several forwards in flight use the same 4-wave cfconv build as a lone forward (flag bit 4 - the 8-wave build,
+        # several forwards in flight use the same 4-wave cfconv build as a lone forward (flag bit 2 - the 8-wave build,
         # two waves per SIMD on one LDS image - measured equal within run-to-run spread: 634 vs 621 M edges/s, and it
-        # costs a lone forward 12 us); MPENGINE_INFLIGHT_CFCONV_FLAGS overrides for experiments
-        if mode == "fused" and self.in_flight > 1 and os.environ.get("MPENGINE_INFLIGHT_CFCONV_FLAGS"):
-            self.model.fused.cfconv_flags = int(os.environ["MPENGINE_INFLIGHT_CFCONV_FLAGS"])
+        # costs a lone forward 12 us)
         # launch groups in flight: the node chains of a union launch (hundreds of tiles) run on half the CUs - flag bit 9 of
         # the node entry points, "several launch sequences in flight" - so that the other sequences' kernels find CUs and
         # every workgroup's weight slices serve twice the tiles (+3 %); single batches (144 tiles) are not affected

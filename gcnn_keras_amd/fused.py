@@ -247,11 +247,10 @@ class FusedSchnet:
             self.node_images = images["node_bf"]
             self.flags_arg |= 64
         # stage 0's node role as a row gather from the input tables of the build chosen above; MPENGINE_NODE_TABLE=0 keeps
-        # the chain.  MPENGINE_STAGE0_EDGE_CAP: cap of stage 0's edge workgroups (multiple of 16), for A/B runs.
+        # the chain.
         self.table = None
         if images.get("table") is not None and os.environ.get("MPENGINE_NODE_TABLE", "1") != "0":
             self.table = images["table"]["node_bf" if self.flags_arg & 64 else "node"]
-        self._edge_cap = (int(os.environ.get("MPENGINE_STAGE0_EDGE_CAP", "0")) // 16 & 255) << 16
         self._own_stream = None     # made on first use (capture / engine.SchnetForward): a slot that is bound, launched
         self.graph = None           # once and dropped never needs one
         self._ring = None
@@ -349,8 +348,7 @@ class FusedSchnet:
             _ffi.call("mp_schnet_stage0_table_f32", _ffi.ptr(b["z"]), self.N, int(p["embedding"].shape[0]),
                       _ffi.ptr(t[0]), _ffi.ptr(t[1]), _ffi.ptr(self.n), _ffi.ptr(self.x), _ffi.ptr(b["idx"]), self.M,
                       _ffi.ptr(b["ns"]), _ffi.ptr(b["es"]), self.G, _ffi.ptr(b["xyz"]), _ffi.ptr(self.recv),
-                      _ffi.ptr(self.send), _ffi.ptr(self.dist), _ffi.ptr(self.flags), self.node_flags | self._edge_cap,
-                      _ffi.stream())
+                      _ffi.ptr(self.send), _ffi.ptr(self.dist), _ffi.ptr(self.flags), self.node_flags, _ffi.stream())
         elif self.sorted or self.M == 0:
             # stage 0: node-input chain and edge preparation in one launch (independent work on disjoint workgroups)
             _ffi.call("mp_schnet_stage0_f32", _ffi.ptr(b["z"]), self.N, _ffi.ptr(p["embedding"]),

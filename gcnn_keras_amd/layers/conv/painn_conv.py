@@ -123,7 +123,7 @@ class PAiNNconv(GraphBaseLayer):
         return ds, dv
 
     def _fused_message(self, node, s, equivariant, rbf, envelope, r_ij, indexlist):
-        """Edge side of the block in one kernel (``mp_painn_message_fused_f32``) when the configuration allows:
+        """Edge side of the block in one kernel (``mp_painn_message_f32``) when the configuration allows:
         128 units, sum pooling, basis <= 32, no gradient requested (forces use the layer sequence)."""
         from ... import _ffi
         from ...autograd import needs_grad
@@ -141,10 +141,11 @@ class PAiNNconv(GraphBaseLayer):
         ds = torch.empty((plan.N, 128), dtype=torch.float32, device=sv.device)
         dv = torch.empty((plan.N, 3, 128), dtype=torch.float32, device=sv.device)
         env = envelope.values.contiguous().view(-1) if self.cutoff is not None else None
-        _ffi.call("mp_painn_message_fused_f32", _ffi.ptr(sv), _ffi.ptr(vv), plan.N, _ffi.ptr(rbf.values.contiguous()),
+        # (z_in = None: no residual adds; ds / dv are fresh buffers, so dv cannot alias v)
+        _ffi.call("mp_painn_message_f32", _ffi.ptr(sv), _ffi.ptr(vv), plan.N, _ffi.ptr(rbf.values.contiguous()),
                   int(rbf.values.shape[-1]), _ffi.ptr(env), _ffi.ptr(r_ij.values.contiguous()),
                   _ffi.ptr(self.lay_w.kernel), _ffi.ptr(self.lay_w.bias), _ffi.ptr(ptr), _ffi.ptr(perm),
-                  _ffi.ptr(plan.col(1).contiguous()), plan.M, _ffi.ptr(ds), _ffi.ptr(dv), _ffi.stream())
+                  _ffi.ptr(plan.col(1).contiguous()), plan.M, None, _ffi.ptr(ds), _ffi.ptr(dv), _ffi.stream())
         return node.with_values(ds), equivariant.with_values(dv)
 
     def get_config(self):

@@ -249,7 +249,9 @@ int mp_edge_prepare_i64_f32(const int64_t* idx, int64_t M, const int64_t* node_s
  * per weight update into the kernel's LDS image by mp_cfconv_pack_f32 (mp_cfconv_packed_floats() floats).
  * recv_sorted ascending; perm (nullable) maps sorted position -> original edge (rbf / send are in original
  * order); out (N,128) must be zero on entry.  flags bit0: fast softplus (v_exp/v_log form, |delta| < 2e-7);
- * bit2 / bit3 force the 8-wave / 4-wave workgroup (default: by tile count). */
+ * bit 2 (value 4) / bit 3 (value 8) force the 8-wave / 4-wave workgroup (default: by tile count); bit 4 (value 16,
+ * "several forwards in flight"): half as many workgroups, each serving twice the tiles.  Bit 5 needs a workspace (below);
+ * these entry points ignore it. */
 int mp_cfconv_packed_floats(void);
 int mp_cfconv_pack_f32(const float* W1, const float* b1, int B, const float* W2, const float* b2, float* packed,
                        mpStream_t stream);
@@ -297,15 +299,6 @@ int mp_cfconv_gauss_diag_f32(const float* x, int64_t N, const float* dist, int b
                              const int32_t* perm, int64_t M, float* out_zeroed, unsigned long long* diag8,
                              mpStream_t stream);
 
-/* PAiNNconv.call edge side, kgcnn/layers/conv/painn_conv.py:99-113, fused (F = units = 128, conv_pool = sum):
- * w = rbf Ww + bw [* env]; sw = s[send] * w; ds[i] = sum sw1; dv[i] = sum (sw2 (x) v[send] + sw3 (x) r_ij) over the edges
- * of receiver i in edge order (CSR ptr / perm as mp_segment_reduce_csr_f32).  s (N,3F) = phi(dense1(z)), v (N,3,F),
- * rbf (M,B<=32), env (M)|NULL, rij (M,3), Ww (B,3F), bw (3F)|NULL; writes ds (N,F), dv (N,3,F) incl. zero rows. */
-int mp_painn_message_fused_f32(const float* s, const float* v, int64_t N, const float* rbf, int B, const float* env,
-                               const float* rij, const float* Ww, const float* bw, const int32_t* ptr,
-                               const int32_t* perm, const int32_t* send, int64_t M, float* ds, float* dv,
-                               mpStream_t stream);
-
 /* ---------------------------------------------------------------- recurrent / edge-network pieces -------- */
 /* One Keras LSTM step from the zero state, as PoolingSet2Set runs it (kgcnn/layers/pool/set2set.py:190: a stateless LSTM
  * layer called on a length-1 sequence): z (R,4U) = x kernel + bias in Keras gate order [i | f | c | o];
@@ -332,8 +325,12 @@ int mp_painn_stage0_f32(const void* numbers /* float32, or int64 if numbers_i64 
                         const float* xyz, const float* frequencies, int num_radial, float bessel_cutoff,
                         int envelope_exponent, float cos_cutoff, int32_t* recv, int32_t* send, int32_t* flags, float* dist,
                         float* rij, float* rbf, float* rbfd, float* env, float* envd, mpStream_t stream);
-/* mp_painn_message_fused_f32 with the residual adds of PAiNN.py:126-127 fused (z_in != NULL: ds := z_in + ds,
- * dv := v + dv; dv must not alias v), four edges in flight per wave, packed FP32 arithmetic. */
+/* PAiNNconv.call edge side, kgcnn/layers/conv/painn_conv.py:99-113, fused (F = units = 128, conv_pool = sum):
+ * w = rbf Ww + bw [* env]; sw = s[send] * w; ds[i] = sum sw1; dv[i] = sum (sw2 (x) v[send] + sw3 (x) r_ij) over the edges
+ * of receiver i in edge order (CSR ptr / perm as mp_segment_reduce_csr_f32).  s (N,3F) = phi(dense1(z)), v (N,3,F),
+ * rbf (M,B<=32), env (M)|NULL, rij (M,3), Ww (B,3F), bw (3F)|NULL; writes ds (N,F), dv (N,3,F) incl. zero rows.
+ * z_in != NULL fuses the residual adds of PAiNN.py:126-127: ds := z_in + ds, dv := v + dv.  dv must not alias v.
+ * Two waves per receiver, four edges in flight per wave, packed FP32 arithmetic. */
 int mp_painn_message_f32(const float* s, const float* v, int64_t N, const float* rbf, int B, const float* env,
                          const float* rij, const float* Ww, const float* bw, const int32_t* ptr, const int32_t* perm,
                          const int32_t* send, int64_t M, const float* z_in, float* ds, float* dv, mpStream_t stream);
@@ -415,10 +412,12 @@ int mp_edge_geometry_bwd_f32(const float* g_d, const float* g_rij, int slices, c
  * flags bit0: fast softplus as in mp_cfconv_fused_f32; bit1: every weight-matrix pointer is an
  * mp_schnet_node_pack_f32 image of the Keras kernel instead of the kernel itself (biases stay plain): the image stores,
  * per wave and lane, the registers of four consecutive k-steps as one float4, so a workgroup loads its weight slices
- * with 16-B instead of strided 4-B reads. */
+ * with 16-B instead of strided 4-B reads.  mp_schnet_node_in_f32, mp_schnet_stage0_f32, mp_schnet_node_update_f32 and
+ * mp_schnet_node_last_f32 (and their _save_ forms) are built for images only: they REQUIRE bit 1 and return MP_EINVAL
+ * without it, before any device work.  mp_schnet_node_residual_f32 alone reads the Keras kernels themselves. */
 int mp_schnet_node_pack_f32(const float* W, int K, int U, float* packed /* K*U floats */, mpStream_t stream);
 /* The same slice order with every element as three bf16 pieces (hi + mid + lo = the FP32 value exactly): flags bit 6
- * (value 64, together with bit 1) makes the node kernels of the FORWARD run their GEMMs on the bf16 matrix pipe as an exact
+ * (value 64) makes the node kernels of the FORWARD run their GEMMs on the bf16 matrix pipe as an exact
  * FP32 emulation (six products per k block, FP32 accumulate: the error of the FP32 matrix instructions at 2.67x their
  * rate).  K % 32 == 0; the image holds K*U*3/2 floats.
  * flags bit 9 (value 512, bf16-piece build): "several launch sequences share the GPU" - a launch with 256 or more 16-node
@@ -437,7 +436,7 @@ int mp_schnet_stage0_f32(const float* numbers, int64_t N, const float* emb, int 
                          const int64_t* node_splits, const int64_t* edge_splits, int64_t G, const float* xyz,
                          int32_t* recv, int32_t* send, float* dist, int32_t* flags, int flags_arg, mpStream_t stream);
 /* The node-input chain as a table: n and x of mp_schnet_node_in_f32 are functions of the node number alone, so the chain
- * runs once per weight update on the numbers 0 .. vocab-1, -1 (same build: flags bits 0, 1, 6 as the forward uses them)
+ * runs once per weight update on the numbers 0 .. vocab-1, -1 (same build: flags bits 0, 1 - required -, 6 as the forward)
  * and fills n_table / x_table, (vocab + 1, 128) each: row r < vocab = the chain's rows for a node with number r, row
  * vocab = its rows for a number outside 0 .. vocab-1 (zero embedding row: b0 resp. b0 Wx).  Bit-identical to the chain by
  * construction.  numbers_ws: (vocab + 1) floats of scratch.  vocab + 1 <= MP_SCHNET_TABLE_MAX_ROWS (both tables: 2 MB, half
@@ -449,8 +448,7 @@ int mp_schnet_embed_table_f32(const float* emb, int vocab, int emb_dim, const fl
 /* mp_schnet_node_in_f32 / mp_schnet_stage0_f32 with the chain replaced by a row gather from the tables: per node the number
  * is read (float32, or int64 with flags bit 8; cast and range rule of the chain) and row r of n_table / x_table is copied
  * to n_out / x_out.  No LDS, no barrier, 256-thread workgroups.  The stage-0 form runs the edge preparation on further
- * workgroups of the same launch (at most 128; flags_arg bits 16-23, if set: the cap in units of 16 workgroups, for A/B
- * runs) and falls back to two launches for large batches as mp_schnet_stage0_f32 does. */
+ * workgroups of the same launch (at most 128) and falls back to two launches for large batches as mp_schnet_stage0_f32 does. */
 int mp_schnet_node_in_table_f32(const float* numbers, int64_t N, int vocab, const float* n_table, const float* x_table,
                                 float* n_out, float* x_out, int flags, mpStream_t stream);
 int mp_schnet_stage0_table_f32(const float* numbers, int64_t N, int vocab, const float* n_table, const float* x_table,

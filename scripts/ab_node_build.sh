@@ -10,5 +10,4 @@ print('$1', round(l['value']/1e6,1), 'M edges/s', round(l['ms_per_step']*1e3,2),
 for r in 1 2 3; do
   $B 2>/dev/null | show "bf16 nodes        "
   MPENGINE_NODE_BF16=0 $B 2>/dev/null | show "fp32 nodes        "
-  MPENGINE_NODE_BF16=0 MPENGINE_INFLIGHT_CFCONV_FLAGS=4 $B 2>/dev/null | show "fp32 nodes+8wave "
 done

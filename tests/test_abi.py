@@ -39,6 +39,17 @@ def test_argument_errors_map_to_python_exceptions():
     assert b"mp_dense_f32" in lib.mp_last_error()
     rc = lib.mp_segment_reduce_csr_f32(9, None, 0, 1, None, None, 0, None, 0, None, None)
     assert rc == _ffi.MP_EINVAL
+    # the SchNet node chains read packed weight images only: flags bit 1 clear is refused before the pointers are looked at
+    for name, call in (
+            ("mp_schnet_node_in_f32", lambda: lib.mp_schnet_node_in_f32(None, 4, None, 10, 64, None, None, None, None, None,
+                                                                        1, None)),
+            ("mp_schnet_node_update_f32", lambda: lib.mp_schnet_node_update_f32(None, 4, None, None, None, None, None, None,
+                                                                                None, 1, None)),
+            ("mp_schnet_node_last_f32", lambda: lib.mp_schnet_node_last_f32(None, 4, None, None, None, None, None, None, None,
+                                                                            None, None, None, 1, None))):
+        assert call() == _ffi.MP_EINVAL
+        message = lib.mp_last_error()
+        assert name.encode() in message and b"flags bit 1" in message
     # zero-sized problems are accepted without touching the device
     assert lib.mp_gather_rows_f32(None, 0, 4, None, 0, 1, _ffi.int32_array([0]), None, None) == _ffi.MP_OK
     assert lib.mp_shift_index_i64(None, 0, 2, None, None, 0, 1, None, None) == _ffi.MP_OK

@@ -168,9 +168,11 @@ def test_graphed_model_replay_matches_eager():
     assert not np.array_equal(gm().cpu().numpy(), eager)
 
 
-@pytest.mark.parametrize("cutoff,shuffle", [(None, False), (5.0, True)])
-def test_painn_conv_fused_message_vs_oracle(cutoff, shuffle):
-    """PAiNNconv.call with the fused edge kernel vs the oracle's layer sequence (painn_conv.py:97-115)."""
+@pytest.mark.parametrize("cutoff,shuffle,bins", [(None, False, 20), (5.0, True, 20), (None, False, 7), (5.0, True, 7)],
+                         ids=["None-False", "5.0-True", "None-False-7", "5.0-True-7"])   # (the 20-bin cases keep their ids)
+def test_painn_conv_fused_message_vs_oracle(cutoff, shuffle, bins):
+    """PAiNNconv.call with the fused edge kernel vs the oracle's layer sequence (painn_conv.py:97-115); 7 bins: the
+    kernel's generic (odd) basis size, with the first 7 rows of the filter kernel."""
     from gcnn_keras_amd.layers.conv.painn_conv import PAiNNconv
     b = synth.md17_like_batch(num_graphs=3, seed=4)
     rng = np.random.default_rng(1)
@@ -187,12 +189,13 @@ def test_painn_conv_fused_message_vs_oracle(cutoff, shuffle):
     p1, p2 = ko.node_position(xyz, ridx)
     d = ko.node_distance_euclidean(p1, p2)
     rij = ko.edge_direction_normalized(p1, p2)
-    rbf = ko.bessel_basis(d, 20, 5.0)
+    rbf = ko.bessel_basis(d, bins, 5.0)
     env = ko.cos_cutoff_envelope(d, cutoff)
     p = {k[len("conv0/"):]: v_ for k, v_ in synth.painn_params(seed=8, random_bias=True).items()
          if k.startswith("conv0/")}
+    p["w/kernel"] = np.ascontiguousarray(p["w/kernel"][:bins])
     lay = PAiNNconv(units=128, cutoff=cutoff)
-    lay.ensure_built([(None, None, 128), (None, None, 3, 128), (None, None, 20), (None, None, 1), (None, None, 3),
+    lay.ensure_built([(None, None, 128), (None, None, 3, 128), (None, None, bins), (None, None, 1), (None, None, 3),
                       (None, None, 2)])
     lay.set_weights([p["dense1/kernel"], p["dense1/bias"], p["phi/kernel"], p["phi/bias"], p["w/kernel"], p["w/bias"]])
     ds, dv = lay([_dev(z.values, z.row_splits), _dev(v.values, v.row_splits), _dev(rbf.values, rbf.row_splits),
