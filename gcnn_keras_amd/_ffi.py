@@ -195,6 +195,11 @@ _SIGNATURES = {
                          c_float, P, c_size_t, P, P, P, P],
     "mp_egnn_edge_grad_f32": [P, c_int64, P, P, c_int64, P, P, P, c_int, c_int, P, c_int, P, c_int, P, P, c_int,
                               c_float, P, P, P],
+    "mp_frac_to_real_f32": [P, P, P, c_int64, c_int64, c_int, P, P],
+    "mp_batchnorm_infer_f32": [P, c_int64, c_int64, P, P, P, P, c_float, P, P],
+    "mp_cgcnn_gate_ws_bytes": [c_int64, P],
+    "mp_cgcnn_gate_f32": [P, P, P, P, P, c_int64, P, c_int, P, c_int64, P, P, P, P, P, P, P, P, c_int, c_int, c_float, P,
+                          c_size_t, P, P],
     "mp_scaler_species_count": [P, c_int, P, c_int64, c_int64, P, P, P, P, P],
     "mp_scaler_fit_ws_bytes": [c_int64, c_int, P],
     "mp_scaler_normal_f64": [P, P, c_int64, P, c_int, c_int, P, c_double, c_int, P, P, P, P, c_size_t, P],

@@ -789,6 +789,49 @@ class LatticeShift(torch.autograd.Function):
         return g, None, None, None
 
 
+class FracToReal(torch.autograd.Function):
+    """``A f`` per row (``mp_frac_to_real_f32``; ``transposed``: ``A^T f``).  Linear in ``f``: the reverse is the same rule
+    with the other flag, so it is differentiable any number of times.  The lattice gets no gradient
+    (``FracToRealCoordinates`` refuses one that requires grad)."""
+
+    @staticmethod
+    def forward(ctx, frac, lattice, row_splits, transposed):
+        from .layers.geom import _frac_to_real_raw
+        ctx.lattice, ctx.row_splits, ctx.transposed = lattice, row_splits, transposed
+        return _frac_to_real_raw(frac, lattice, row_splits, transposed)
+
+    @staticmethod
+    def backward(ctx, g):
+        return FracToReal.apply(g.contiguous(), ctx.lattice, ctx.row_splits, not ctx.transposed), None, None, None
+
+
+class BatchNormInfer(torch.autograd.Function):
+    """Inference batch normalisation (``mp_batchnorm_infer_f32``) as a function of its input alone: the reverse is
+    ``g * inv`` on the same entry point, linear in ``g``.  The four vectors are constants (no weight gradients)."""
+
+    @staticmethod
+    def forward(ctx, x, layer):
+        ctx.layer = layer
+        return layer._infer_raw(x, reverse=False)
+
+    @staticmethod
+    def backward(ctx, g):
+        return BatchNormInferScale.apply(g, ctx.layer), None
+
+
+class BatchNormInferScale(torch.autograd.Function):
+    """``g * inv``: its own reverse."""
+
+    @staticmethod
+    def forward(ctx, g, layer):
+        ctx.layer = layer
+        return layer._infer_raw(g, reverse=True)
+
+    @staticmethod
+    def backward(ctx, h):
+        return BatchNormInferScale.apply(h, ctx.layer), None
+
+
 # ------------------------------------------------------------------------------------------------ HDNNP2nd
 _coordinate_hessian_discarded = [False]
 

@@ -246,6 +246,23 @@ __global__ void lattice_shift_kernel(const float* __restrict__ pos, const int64_
   }
 }
 
+// FracToRealCoordinates (kgcnn/layers/geom.py:1012-1052): the einsum 'ij,ikj->ik', r_k = (f_0 A[k][0] + f_1 A[k][1]) +
+// f_2 A[k][2] - the lattice matrix times the row, whatever the reference's docstring says.  transposed: the reverse,
+// g_j = (r_0 A[0][j] + r_1 A[1][j]) + r_2 A[2][j].
+__global__ void frac_to_real_kernel(const float* __restrict__ frac, const float* __restrict__ lattice,
+                                    const int64_t* __restrict__ row_splits, int64_t G, int64_t M, int transposed,
+                                    float* __restrict__ out) {
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
+  for (int64_t e = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; e < M; e += stride) {
+    const float* lat = lattice + mp_owner_of(row_splits, G, e) * 9;
+    const float f0 = frac[e * 3 + 0], f1 = frac[e * 3 + 1], f2 = frac[e * 3 + 2];
+    for (int k = 0; k < 3; ++k) {
+      const int i0 = transposed ? k : 3 * k, step = transposed ? 3 : 1;
+      out[e * 3 + k] = (f0 * lat[i0] + f1 * lat[i0 + step]) + f2 * lat[i0 + 2 * step];
+    }
+  }
+}
+
 unsigned receiver_grid(int64_t N) { return static_cast<unsigned>(N < 256 * 64 ? (N < 1 ? 1 : N) : 256 * 64); }
 
 }  // namespace
@@ -259,6 +276,16 @@ int mp_lattice_shift_f32(const float* pos, const int64_t* image, const float* la
   MP_REQUIRE(pos && image && lattice && edge_splits && out && G > 0, "mp_lattice_shift_f32: null pointer / no graphs");
   lattice_shift_kernel<<<mp::grid_for(M), 256, 0, mp::as_stream(stream)>>>(pos, image, lattice, edge_splits, G, M, out);
   return mp::check_launch("mp_lattice_shift_f32");
+}
+
+int mp_frac_to_real_f32(const float* frac, const float* lattice, const int64_t* row_splits, int64_t G, int64_t M,
+                        int transposed, float* out, mpStream_t stream) {
+  MP_REQUIRE(G >= 0 && M >= 0, "mp_frac_to_real_f32: bad sizes");
+  if (M == 0) return MP_OK;
+  MP_REQUIRE(frac && lattice && row_splits && out && G > 0, "mp_frac_to_real_f32: null pointer / no graphs");
+  frac_to_real_kernel<<<mp::grid_for(M), 256, 0, mp::as_stream(stream)>>>(frac, lattice, row_splits, G, M,
+                                                                          transposed ? 1 : 0, out);
+  return mp::check_launch("mp_frac_to_real_f32");
 }
 
 int mp_radius_graph_periodic_workspace_bytes(int64_t N, size_t* bytes_out_host) {

@@ -6,7 +6,7 @@ from .. import _ffi
 from ..ops.axis import get_positive_axis
 from .base import GraphBaseLayer
 from .gather import GatherNodesSelection
-from .modules import LazyMultiply, LazySubtract
+from .modules import LazyAdd, LazyMultiply, LazySubtract
 
 
 class NodePosition(GraphBaseLayer):
@@ -85,6 +85,69 @@ class ShiftPeriodicLattice(GraphBaseLayer):
         if needs_grad(x.values):
             return ei.with_values(LatticeShift.apply(x.values, ei.values, lattice, ei.row_splits))
         return ei.with_values(_lattice_shift_raw(x.values, ei.values, lattice, ei.row_splits))
+
+
+class DisplacementVectorsUnitCell(GraphBaseLayer):
+    r"""``f_i - (f_j + m_ij)`` for fractional coordinates ``f`` ``(batch, [N], 3)``, edge indices ``(batch, [M], 2)`` and
+    cell translations ``m`` ``(batch, [M], 3)`` (kgcnn/layers/geom.py:964-1008): gather, add, subtract, as the
+    reference composes it.  ``cell_translations`` is float32; an int64 tensor (``range_image`` of ``SetRangePeriodic``)
+    is cast."""
+
+    weight_gradients = True   # layers/base.py: the layer has no weights
+
+    def __init__(self, **kwargs):
+        super().__init__(**kwargs)
+        self.gather_node_positions = NodePosition()
+        self.lazy_add = LazyAdd()
+        self.lazy_sub = LazySubtract()
+
+    def call(self, inputs, **kwargs):
+        frac_coords, edge_indices, cell_translations = inputs[0], inputs[1], inputs[2]
+        if cell_translations.values.dtype == torch.int64:
+            cell_translations = cell_translations.with_values(cell_translations.values.to(torch.float32))
+        in_frac_coords, out_frac_coords = self.gather_node_positions([frac_coords, edge_indices], **kwargs)
+        out_frac_coords = self.lazy_add([out_frac_coords, cell_translations], **kwargs)
+        return self.lazy_sub([in_frac_coords, out_frac_coords], **kwargs)
+
+
+def _frac_to_real_raw(frac, lattice, row_splits, transposed=False):
+    _ffi.require_device(frac, lattice, row_splits)
+    f, lat = frac.contiguous(), lattice.contiguous()
+    out = torch.empty_like(f)
+    _ffi.call("mp_frac_to_real_f32", _ffi.ptr(f), _ffi.ptr(lat), _ffi.ptr(row_splits), int(lat.shape[0]),
+              int(f.shape[0]), 1 if transposed else 0, _ffi.ptr(out), _ffi.stream())
+    return out
+
+
+class FracToRealCoordinates(GraphBaseLayer):
+    r"""Real-space from fractional coordinates ``(batch, [N], 3)`` and one lattice matrix ``(batch, 3, 3)`` per graph
+    (kgcnn/layers/geom.py:1012-1052) on ``mp_frac_to_real_f32``.  The reference's einsum is ``'ij,ikj->ik'``:
+    ``r_k = sum_j f_j A[k][j]``, that is :math:`\mathbf{A} \vec{f}` - NOT the :math:`\vec{f} \mathbf{A}` with lattice
+    vectors in rows that its docstring promises.  The code is mirrored: a lattice in the row convention (pymatgen,
+    ``SetRangePeriodic``) has to be passed **transposed**.  Linear in the coordinates (the reverse is the transposed
+    product, differentiable any number of times); a lattice that requires grad raises."""
+
+    weight_gradients = True   # layers/base.py: the layer has no weights
+
+    def call(self, inputs, **kwargs):
+        from ..ragged import RaggedTensor
+        if len(inputs) != 2:
+            raise ValueError("FracToRealCoordinates expects [frac_coordinates, lattice_matrix]")
+        frac, lattice = self.assert_ragged_input_rank(inputs[0], ragged_rank=1), inputs[1]
+        if isinstance(lattice, RaggedTensor) or not torch.is_tensor(lattice):
+            raise TypeError("FracToRealCoordinates expects the lattice as a dense tensor of shape (batch, 3, 3)")
+        if frac.values.dtype != torch.float32 or lattice.dtype != torch.float32:
+            raise TypeError("FracToRealCoordinates expects float32 coordinates and lattice")
+        if tuple(lattice.shape) != (frac.nrows(), 3, 3):
+            raise ValueError("lattice must have shape (%d, 3, 3), got %s" % (frac.nrows(), tuple(lattice.shape)))
+        if frac.values.dim() != 2 or int(frac.values.shape[1]) != 3:
+            raise ValueError("fractional coordinates must be (batch, [N], 3), got %s" % (tuple(frac.values.shape),))
+        if lattice.requires_grad and torch.is_grad_enabled():
+            raise NotImplementedError("gradients with respect to the lattice (stress) are not implemented")
+        from ..autograd import FracToReal, needs_grad
+        if needs_grad(frac.values):
+            return frac.with_values(FracToReal.apply(frac.values, lattice, frac.row_splits, False))
+        return frac.with_values(_frac_to_real_raw(frac.values, lattice, frac.row_splits))
 
 
 class EuclideanNorm(GraphBaseLayer):

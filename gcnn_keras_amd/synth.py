@@ -630,3 +630,46 @@ def periodic_structures(num_graphs=128, seed=5678, min_atoms=4, max_atoms=30, de
         numbers.append(rng.choice(np.array([1, 6, 7, 8, 14], dtype=np.int64), size=int(n)))
     return {"node_number": np.concatenate(numbers), "node_coordinates": np.concatenate(coords, axis=0),
             "node_splits": _splits(sizes), "graph_lattice": np.stack(lattices)}
+
+
+def cgcnn_batch(structures=None, edges=None, **kwargs):
+    """CGCNN inputs of periodic structures: ``structures`` is a batch of :func:`periodic_structures` (made with
+    ``kwargs`` when left out).  Adds ``node_frac_coordinates`` (float32; ``x L^-1`` with the float64 inverse of the
+    float32 lattice) and ``lattice_matrix``, the lattice TRANSPOSED - the convention ``FracToRealCoordinates`` computes
+    with (``A f``, see literature/CGCNN.py).  ``edges``: a dict with ``edge_indices`` (or ``range_indices``),
+    ``edge_image`` (or ``range_image``) and ``edge_splits`` from a neighbour search (``SetRangePeriodic``, or a brute
+    force) - copied in as ``edge_indices``, ``cell_translations`` (float32) and ``edge_splits``."""
+    b = dict(periodic_structures(**kwargs) if structures is None else structures)
+    ns, lat = np.asarray(b["node_splits"]), np.asarray(b["graph_lattice"], dtype=np.float64)
+    xyz = np.asarray(b["node_coordinates"], dtype=np.float64).reshape(-1, 3)
+    frac = np.zeros_like(xyz)
+    for g in range(len(ns) - 1):
+        frac[ns[g]:ns[g + 1]] = xyz[ns[g]:ns[g + 1]] @ np.linalg.inv(lat[g])
+    b["node_frac_coordinates"] = frac.astype(np.float32)
+    b["lattice_matrix"] = np.ascontiguousarray(np.transpose(lat, (0, 2, 1))).astype(np.float32)
+    if edges is not None:
+        idx = edges["edge_indices"] if "edge_indices" in edges else edges["range_indices"]
+        img = edges["edge_image"] if "edge_image" in edges else edges["range_image"]
+        b["edge_indices"] = np.asarray(idx, dtype=np.int64).reshape(-1, 2)
+        b["cell_translations"] = np.asarray(img).reshape(-1, 3).astype(np.float32)
+        b["edge_splits"] = np.asarray(edges["edge_splits"], dtype=np.int64)
+    return b
+
+
+def cgcnn_params(model, seed=31):
+    """Random weights for a built CGCNN ``model`` in ``model.weights`` order: Glorot-uniform kernels, biases in +-0.1,
+    embeddings in +-0.05, and non-trivial batch-norm vectors (gamma in [0.5, 1.5], beta in +-0.3, moving mean in +-0.5,
+    moving variance in [0.5, 2])."""
+    rng = np.random.default_rng(seed)
+    draw = {"embeddings": (-0.05, 0.05), "bias": (-0.1, 0.1), "gamma": (0.5, 1.5), "beta": (-0.3, 0.3),
+            "moving_mean": (-0.5, 0.5), "moving_variance": (0.5, 2.0)}
+    p = {}
+    for i, (name, t) in enumerate(model.weights):
+        shape = tuple(int(s) for s in t.shape)
+        leaf = name.rsplit("/", 1)[-1]
+        if leaf in draw:
+            v = rng.uniform(draw[leaf][0], draw[leaf][1], size=shape)
+        else:
+            v = glorot_uniform(rng, shape[0], shape[-1], shape=shape)
+        p["%03d/%s" % (i, name)] = np.asarray(v, dtype=np.float32)
+    return p
