@@ -200,6 +200,9 @@ _SIGNATURES = {
     "mp_cgcnn_gate_ws_bytes": [c_int64, P],
     "mp_cgcnn_gate_f32": [P, P, P, P, P, c_int64, P, c_int, P, c_int64, P, P, P, P, P, P, P, P, c_int, c_int, c_float, P,
                           c_size_t, P, P],
+    "mp_megnet_edge_ws_bytes": [c_int64, P],
+    "mp_megnet_edge_f32": [P, P, c_int64, P, P, c_int64, P, c_int, c_int, c_int, P, c_int64, P, P, P, P, P, P, P, c_int,
+                           c_int, c_int, c_int, c_float, c_int, P, c_size_t, P, P, P],
     "mp_scaler_species_count": [P, c_int, P, c_int64, c_int64, P, P, P, P, P],
     "mp_scaler_fit_ws_bytes": [c_int64, c_int, P],
     "mp_scaler_normal_f64": [P, P, c_int64, P, c_int, c_int, P, c_double, c_int, P, P, P, P, c_size_t, P],

@@ -184,6 +184,10 @@ class GatherState(GraphBaseLayer):
         for d in envc.shape[1:]:
             elems *= int(d)
         n = int(target.values.shape[0])
+        from ..autograd import PoolGraphAdjoint, needs_grad
+        if needs_grad(envc):
+            # the repeat with its reverse rule (the per-graph sum): PoolGraph's adjoint with op = sum is this layer
+            return target.with_values(PoolGraphAdjoint.apply(envc, _ffi.MP_SUM, target.row_splits, target.nrows(), n))
         out = torch.empty((n,) + tuple(envc.shape[1:]), dtype=envc.dtype, device=envc.device)
         _ffi.call("mp_repeat_rows_f32", _ffi.ptr(envc), _ffi.ptr(target.row_splits), target.nrows(), max(elems, 1), n,
                   _ffi.ptr(out), _ffi.stream())

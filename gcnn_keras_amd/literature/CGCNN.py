@@ -32,7 +32,7 @@ from ..layers.geom import (DisplacementVectorsUnitCell, EuclideanNorm, FracToRea
 from ..layers.mlp import MLP
 from ..layers.modules import Dense, LazySubtract, OptionalInputEmbedding
 from ..layers.pooling import PoolingNodes
-from ..model.utils import Model, update_model_kwargs
+from ..model.utils import RouteSwitchModel, update_model_kwargs
 from ..ragged import RaggedTensor
 
 __model_version__ = "2022.11.25"
@@ -66,27 +66,12 @@ model_crystal_default = {
 }
 
 
-class _CgcnnModel(Model):
-    """``Model`` with the ``use_fused_gate`` switch over all layers: changing it drops the captured HIP graphs, which
-    hold the route they were captured on."""
+class _CgcnnModel(RouteSwitchModel):
+    """``Model`` with the ``use_fused_gate`` switch over all layers."""
 
+    switch_attr, switch_layers_attr = "use_fused_gate", "conv_layers"
     conv_layers = ()
-
-    @property
-    def use_fused_gate(self):
-        return all(lay.use_fused_gate for lay in self.conv_layers)
-
-    @use_fused_gate.setter
-    def use_fused_gate(self, value):
-        if any(lay.use_fused_gate != bool(value) for lay in self.conv_layers):
-            self.release_graphs()
-        for lay in self.conv_layers:
-            lay.use_fused_gate = bool(value)
-
-    def _graph_key(self, inputs):
-        # the route is part of the identity of a captured graph (a per-layer switch flipped behind the model's back)
-        key = Model._graph_key(inputs)
-        return None if key is None else key + (tuple(lay.use_fused_gate for lay in self.conv_layers),)
+    use_fused_gate = RouteSwitchModel.switch
 
 
 def _float32(x):

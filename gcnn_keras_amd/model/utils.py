@@ -294,3 +294,29 @@ class Model:
                 raise ValueError("Shape mismatch for %s: %s vs %s" % (n, tuple(a.shape), tuple(t.shape)))
             with torch.no_grad():
                 t.copy_(torch.from_numpy(a))
+
+
+class RouteSwitchModel(Model):
+    """``Model`` over layers that each carry a boolean route switch, e.g. ``use_fused_gate``: the model-level switch sets
+    it on every one of them and drops the captured HIP graphs, which hold the route they were captured on.  A subclass
+    names the layers' attribute (``switch_attr``) and the model attribute that lists the layers (``switch_layers_attr``)
+    and exposes ``RouteSwitchModel.switch`` under the switch's name."""
+
+    switch_attr = None
+    switch_layers_attr = None
+
+    def _switches(self):
+        return tuple(getattr(lay, self.switch_attr) for lay in getattr(self, self.switch_layers_attr))
+
+    def _set_switch(self, value):
+        if any(flag != bool(value) for flag in self._switches()):
+            self.release_graphs()
+        for lay in getattr(self, self.switch_layers_attr):
+            setattr(lay, self.switch_attr, bool(value))
+
+    switch = property(lambda self: all(self._switches()), _set_switch)
+
+    def _graph_key(self, inputs):
+        # the route is part of the identity of a captured graph (a per-layer switch flipped behind the model's back)
+        key = Model._graph_key(inputs)
+        return None if key is None else key + (self._switches(),)
