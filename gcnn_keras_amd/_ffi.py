@@ -26,6 +26,7 @@ MP_SCALER_MAX_NUMBER, MP_SCALER_CHUNK_ROWS, MP_SCALER_MAX_STATES = 95, 256, 32  
 # include/mpengine.h: limits and flag bits of the periodic neighbour search
 MP_PERIODIC_MAX_HITS, MP_PERIODIC_MAX_IMAGE, MP_PERIODIC_MAX_CANDIDATES = 1024, 511, 1048576
 MP_PERIODIC_FLAG_CAPACITY, MP_PERIODIC_FLAG_IMAGE_RANGE, MP_PERIODIC_FLAG_SINGULAR = 1, 2, 4
+MP_CMPNN_EDGE_TILE, MP_GRU_RAGGED_MAX_UNITS = 64, 512   # include/mpengine.h
 
 ACTIVATION_CODES = {
     None: 0, "linear": 0, "relu": 1, "kgcnn>shifted_softplus": 2, "shifted_softplus": 2, "softplus": 3,
@@ -203,6 +204,9 @@ _SIGNATURES = {
     "mp_megnet_edge_ws_bytes": [c_int64, P],
     "mp_megnet_edge_f32": [P, P, c_int64, P, P, c_int64, P, c_int, c_int, c_int, P, c_int64, P, P, P, P, P, P, P, c_int,
                            c_int, c_int, c_int, c_float, c_int, P, c_size_t, P, P, P],
+    "mp_cmpnn_boost_f32": [P, P, c_int64, c_int64, P, P, c_int64, c_int, c_int, P, P],
+    "mp_directed_edge_update_f32": [P, c_int64, P, P, c_int64, c_int64, P, P, P, P, c_int, c_int, c_float, P, P, P],
+    "mp_gru_ragged_last_f32": [P, c_int64, P, c_int64, P, P, c_int64, c_int, c_int, P, P],
     "mp_scaler_species_count": [P, c_int, P, c_int64, c_int64, P, P, P, P, P],
     "mp_scaler_fit_ws_bytes": [c_int64, c_int, P],
     "mp_scaler_normal_f64": [P, P, c_int64, P, c_int, c_int, P, c_double, c_int, P, P, P, P, c_size_t, P],

@@ -5,7 +5,11 @@
 //  * GRUUpdate (kgcnn/layers/conv/mpnn_conv.py:111-210) is one Keras GRUCell step (reset_after = True) on the flat node
 //    values: two GEMMs + the combine below;
 //  * MatMulMessages (mpnn_conv.py:69-108) is a per-edge matrix-vector product with the (M,F,F) matrices the edge network
-//    produced: memory bound on the matrices (16 KB per edge at F = 64), read once with 16-B loads.
+//    produced: memory bound on the matrices (16 KB per edge at F = 64), read once with 16-B loads;
+//  * the GRU readout of CMPNN (kgcnn/literature/CMPNN.py:157) is a Keras GRU over every graph's node sequence: the input
+//    GEMM runs on the matrix cores (mp_dense_f32), the recurrence is one launch of this file.
+#include <type_traits>
+
 #include "mp_common.h"
 
 namespace {
@@ -83,9 +87,194 @@ __global__ void batched_matvec_generic_kernel(const float* __restrict__ mat, con
   }
 }
 
+// Keras GRU (reset_after = True) over the node sequence of every graph, state after the last node (the readout of
+// kgcnn/literature/CMPNN.py:157).  The whole recurrence is this one launch: the loop over the sequence runs in here.
+// A workgroup of 8 waves owns 16 graphs = the rows of one A operand of v_mfma_f32_16x16x4_f32 (4 and 8 graphs per
+// workgroup measured the same: DESIGN 3.20); their states live in LDS (row stride = 4 mod 64 floats: the 64 lanes of an A read hit 64 banks).
+// Per step wave w takes the 16-column blocks w, w + 8, ... of the state (up to four) and computes the z, r and h blocks of
+// `state R` for all of them in ONE pass over k, so the three recurrent pre-activations of one (graph, column) meet in one
+// lane and the combine is mp_gru_combine_f32's, in its order.  R (u x 3u, 1.08 MB at u = 300) does not fit a workgroup: its
+// slabs are re-read (from L2) in every step, and a step is a chain of such round trips - so the loads of several k steps
+// for every block and gate of the wave (GRU_LOADS x 3 = 36) are issued together, in front of their MFMAs: 19 round trips per
+// step instead of one per block, gate and k group.  A graph whose sequence has ended keeps its state while the tile runs
+// to its longest member; a graph without nodes leaves the zero state.
+constexpr int GRU_ROWS = 16;
+constexpr int GRU_THREADS = 512;
+constexpr int GRU_WAVES = GRU_THREADS / 64;
+constexpr int GRU_LOADS = 12;   // k steps x blocks whose three slab loads are in flight together (36 loads)
+constexpr int GRU_MAX_UNITS = MP_GRU_RAGGED_MAX_UNITS;
+constexpr int GRU_MAX_BLOCKS = (GRU_MAX_UNITS / 16 + GRU_WAVES - 1) / GRU_WAVES;   // column blocks of one wave
+constexpr int GRU_MAX_STRIDE = ((GRU_MAX_UNITS + 63) / 64) * 64 + 4;
+static_assert(GRU_MAX_BLOCKS == 4, "the step below is instantiated for one to four blocks per wave");
+
+typedef float gru_f32x4 __attribute__((ext_vector_type(4)));
+
+__global__ __launch_bounds__(GRU_THREADS) void gru_ragged_last_kernel(
+    const float* __restrict__ mx, int64_t n_nodes, const int64_t* __restrict__ splits, int64_t G,
+    const float* __restrict__ R, const float* __restrict__ b_rec, int U, int act, int rec_act,
+    float* __restrict__ out) {
+  __shared__ float hL[GRU_ROWS * GRU_MAX_STRIDE];
+  __shared__ long long startL[GRU_ROWS];
+  __shared__ int lenL[GRU_ROWS];
+
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int lc = lane & 15, kq = lane >> 4;
+  const int S = ((U + 63) / 64) * 64 + 4;
+  const int64_t g0 = static_cast<int64_t>(blockIdx.x) * GRU_ROWS;
+  const int U3 = 3 * U;
+
+  if (t < GRU_ROWS) {
+    const int64_t g = g0 + t;
+    int64_t a = 0, b = 0;
+    if (g < G) {
+      a = splits[g];
+      b = splits[g + 1];
+      a = a < 0 ? 0 : (a > n_nodes ? n_nodes : a);
+      b = b < a ? a : (b > n_nodes ? n_nodes : b);
+    }
+    startL[t] = a;
+    const int64_t len = b - a;
+    lenL[t] = len > 0x7fffffff ? 0x7fffffff : static_cast<int>(len);
+  }
+  for (int i = t; i < GRU_ROWS * S; i += GRU_THREADS) hL[i] = 0.0f;
+  __syncthreads();
+  int steps = 0;
+#pragma unroll
+  for (int r = 0; r < GRU_ROWS; ++r) steps = lenL[r] > steps ? lenL[r] : steps;
+
+  const int blocks = (U + 15) / 16;
+  const int my_blocks = wave < blocks ? (blocks - wave + GRU_WAVES - 1) / GRU_WAVES : 0;   // wave-uniform
+  const int ksteps = U / 4;
+  float hnew[GRU_MAX_BLOCKS][4];
+
+  // phase 1 of a step for a wave with NB blocks: its blocks of `state R` and the combine, in registers (the states in
+  // LDS are only read)
+  auto advance = [&](int step, auto nb_tag) {
+    constexpr int NB = decltype(nb_tag)::value;
+    constexpr int GRU_KGROUP = GRU_LOADS / NB;
+    int colc[NB];
+#pragma unroll
+    for (int j = 0; j < NB; ++j) {
+      const int col = 16 * (wave + j * GRU_WAVES) + lc;
+      colc[j] = col < U ? col : U - 1;   // the last block may be partial: work on a column inside, drop the result
+    }
+    gru_f32x4 az[NB], ar[NB], ah[NB];
+#pragma unroll
+    for (int j = 0; j < NB; ++j)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) { az[j][i] = 0.0f; ar[j][i] = 0.0f; ah[j][i] = 0.0f; }
+    const float* ap = hL + lc * S + kq;
+    const float* bp = R + kq * U3;   // offsets into R stay below 3 u^2 < 2^20
+    int s = 0;
+    for (; s + GRU_KGROUP <= ksteps; s += GRU_KGROUP) {
+      float a[GRU_KGROUP], wz[NB][GRU_KGROUP], wr[NB][GRU_KGROUP], wh[NB][GRU_KGROUP];
+#pragma unroll
+      for (int q = 0; q < GRU_KGROUP; ++q) {
+        const float* bs = bp + 4 * (s + q) * U3;
+        a[q] = ap[4 * (s + q)];
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+          wz[j][q] = bs[colc[j]];
+          wr[j][q] = bs[U + colc[j]];
+          wh[j][q] = bs[2 * U + colc[j]];
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < GRU_KGROUP; ++q) {
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+          az[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[q], wz[j][q], az[j], 0, 0, 0);
+          ar[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[q], wr[j][q], ar[j], 0, 0, 0);
+          ah[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[q], wh[j][q], ah[j], 0, 0, 0);
+        }
+      }
+    }
+    for (; s < ksteps; ++s) {
+      const float a = ap[4 * s];
+      const float* bs = bp + 4 * s * U3;
+#pragma unroll
+      for (int j = 0; j < NB; ++j) {
+        az[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bs[colc[j]], az[j], 0, 0, 0);
+        ar[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bs[U + colc[j]], ar[j], 0, 0, 0);
+        ah[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bs[2 * U + colc[j]], ah[j], 0, 0, 0);
+      }
+    }
+    // the input pre-activations of the lane's (graph, column) pairs, then the combine
+    bool live[4];
+    size_t xrow[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int row = 4 * kq + i;
+      live[i] = step < lenL[row];
+      xrow[i] = static_cast<size_t>(live[i] ? startL[row] + step : 0) * U3;
+    }
+#pragma unroll
+    for (int j = 0; j < NB; ++j) {
+      float xz[4], xr[4], xh[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float* xp = mx + xrow[i] + colc[j];
+        xz[i] = live[i] ? xp[0] : 0.0f;
+        xr[i] = live[i] ? xp[U] : 0.0f;
+        xh[i] = live[i] ? xp[2 * U] : 0.0f;
+      }
+      const float bz = b_rec ? b_rec[colc[j]] : 0.0f, br = b_rec ? b_rec[U + colc[j]] : 0.0f,
+                  bh = b_rec ? b_rec[2 * U + colc[j]] : 0.0f;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float hold = hL[(4 * kq + i) * S + colc[j]];
+        const float zg = mp_apply_act(rec_act, 0.0f, xz[i] + (az[j][i] + bz));
+        const float rg = mp_apply_act(rec_act, 0.0f, xr[i] + (ar[j][i] + br));
+        const float hh = mp_apply_act(act, 0.0f, xh[i] + rg * (ah[j][i] + bh));
+        const float hn = zg * hold + (1.0f - zg) * hh;
+        hnew[j][i] = live[i] ? hn : hold;
+      }
+    }
+  };
+
+  for (int step = 0; step < steps; ++step) {
+    if (my_blocks == 4) advance(step, std::integral_constant<int, 4>());
+    else if (my_blocks == 3) advance(step, std::integral_constant<int, 3>());
+    else if (my_blocks == 2) advance(step, std::integral_constant<int, 2>());
+    else if (my_blocks == 1) advance(step, std::integral_constant<int, 1>());
+    __syncthreads();
+    // phase 2: the new states
+#pragma unroll
+    for (int j = 0; j < GRU_MAX_BLOCKS; ++j) {
+      const int col = 16 * (wave + j * GRU_WAVES) + lc;
+      if (j < my_blocks && col < U) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) hL[(4 * kq + i) * S + col] = hnew[j][i];
+      }
+    }
+    __syncthreads();
+  }
+  for (int i = t; i < GRU_ROWS * U; i += GRU_THREADS) {
+    const int row = i / U, col = i - row * U;
+    if (g0 + row < G) out[static_cast<size_t>(g0 + row) * U + col] = hL[row * S + col];
+  }
+}
+
 }  // namespace
 
 extern "C" {
+
+int mp_gru_ragged_last_f32(const float* mx, int64_t n_nodes, const int64_t* row_splits, int64_t G, const float* R,
+                           const float* b_rec, int64_t U, int act, int rec_act, float* out, mpStream_t stream) {
+  const char* what = "mp_gru_ragged_last_f32";
+  MP_REQUIRE(n_nodes >= 0 && G >= 0, "%s: bad sizes", what);
+  MP_REQUIRE(U >= 4 && U % 4 == 0 && U <= GRU_MAX_UNITS, "%s: units must be a multiple of 4, at most %d, got %lld", what,
+             GRU_MAX_UNITS, (long long)U);
+  MP_REQUIRE(act >= MP_ACT_LINEAR && act <= MP_ACT_LAST && rec_act >= MP_ACT_LINEAR && rec_act <= MP_ACT_LAST,
+             "%s: unknown activation", what);
+  if (G == 0) return MP_OK;
+  MP_REQUIRE(row_splits && R && out && (n_nodes == 0 || mx), "%s: null pointer", what);
+  const int64_t grid = mp::ceil_div(G, GRU_ROWS);
+  MP_REQUIRE(grid < (int64_t{1} << 31), "%s: grid too large", what);
+  gru_ragged_last_kernel<<<static_cast<unsigned>(grid), GRU_THREADS, 0, mp::as_stream(stream)>>>(
+      mx, n_nodes, row_splits, G, R, b_rec, static_cast<int>(U), act, rec_act, out);
+  return mp::check_launch(what);
+}
 
 int mp_lstm_zero_state_f32(const float* z, int64_t R, int64_t U, int act, int rec_act, float* out, mpStream_t stream) {
   MP_REQUIRE(R >= 0 && U >= 1, "mp_lstm_zero_state_f32: bad sizes");

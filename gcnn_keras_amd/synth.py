@@ -673,3 +673,58 @@ def cgcnn_params(model, seed=31):
             v = glorot_uniform(rng, shape[0], shape[-1], shape=shape)
         p["%03d/%s" % (i, name)] = np.asarray(v, dtype=np.float32)
     return p
+
+
+def cmpnn_batch(num_graphs=128, seed=6789, min_atoms=6, max_atoms=19, max_rings=3, node_types=10, edge_types=4,
+                node_features=12, edge_features=8):
+    """Molecule-like graphs for CMPNN / DMPNN: per graph a random tree over ``n`` atoms (uniform in ``[min_atoms,
+    max_atoms]``) plus up to ``max_rings`` ring-closing bonds, every bond in both directions, the directed edges sorted by
+    (receiver, sender).  ``edge_indices_reverse`` ``(M, 1)`` holds, per edge, the position of its reverse edge in the
+    graph's own list.  Integer ``node_number`` (1..``node_types``) and ``edge_number`` (1..``edge_types``, equal for both
+    directions of a bond) feed the embedding inputs; ``node_attributes`` / ``edge_attributes`` are float32 features, normal
+    times 0.3, for the feature inputs."""
+    rng = np.random.default_rng(seed)
+    sizes = rng.integers(min_atoms, max_atoms + 1, size=num_graphs)
+    idx, rev, etype, counts = [], [], [], []
+    for n in sizes:
+        n = int(n)
+        bonds = {(int(rng.integers(0, a)), a) for a in range(1, n)}
+        for _ in range(int(rng.integers(0, max_rings + 1))):
+            a, b = (int(v) for v in rng.choice(n, size=2, replace=False))
+            bonds.add((min(a, b), max(a, b)))
+        kind = {bond: int(rng.integers(1, edge_types + 1)) for bond in sorted(bonds)}
+        directed = sorted([(a, b) for a, b in bonds] + [(b, a) for a, b in bonds])
+        where = {e: i for i, e in enumerate(directed)}
+        idx.append(np.array(directed, dtype=np.int64).reshape(-1, 2))
+        rev.append(np.array([where[(b, a)] for a, b in directed], dtype=np.int64).reshape(-1, 1))
+        etype.append(np.array([kind[(min(a, b), max(a, b))] for a, b in directed], dtype=np.int64))
+        counts.append(len(directed))
+    n_total, m_total = int(np.sum(sizes)), int(np.sum(counts))
+    return {"node_number": rng.integers(1, node_types + 1, size=n_total).astype(np.int64),
+            "edge_number": np.concatenate(etype),
+            "node_attributes": (0.3 * rng.normal(size=(n_total, node_features))).astype(np.float32),
+            "edge_attributes": (0.3 * rng.normal(size=(m_total, edge_features))).astype(np.float32),
+            "edge_indices": np.concatenate(idx, axis=0), "edge_indices_reverse": np.concatenate(rev, axis=0),
+            "node_splits": _splits(sizes), "edge_splits": _splits(counts)}
+
+
+def cmpnn_params(model, seed=41, dense_scale=0.5):
+    """Random weights for a built CMPNN ``model`` in ``model.weights`` order: Dense kernels Glorot-uniform times
+    ``dense_scale``, the GRU's two kernels full Glorot-uniform, biases in +-0.1, embeddings in +-0.5.  The booster
+    multiplies a sum by a max, so states grow quadratically per round: with full-scale Dense kernels they reach 1e3-1e5
+    after four rounds and float32 pipelines part by 1e-5; half scale keeps them O(1)."""
+    rng = np.random.default_rng(seed)
+    p = {}
+    for i, (name, t) in enumerate(model.weights):
+        shape = tuple(int(s) for s in t.shape)
+        leaf = name.rsplit("/", 1)[-1]
+        if leaf == "embeddings":
+            v = rng.uniform(-0.5, 0.5, size=shape)
+        elif leaf == "bias":
+            v = rng.uniform(-0.1, 0.1, size=shape)
+        elif "gru_cell" in name:
+            v = glorot_uniform(rng, shape[0], shape[-1], shape=shape)
+        else:
+            v = dense_scale * glorot_uniform(rng, shape[0], shape[-1], shape=shape)
+        p["%03d/%s" % (i, name)] = np.asarray(v, dtype=np.float32)
+    return p
