@@ -432,6 +432,15 @@ def workspace_bytes(name, *args):
     return nbytes.value
 
 
+def float_workspace(name, *args, device, none_if_empty=False):
+    """``(ws, nbytes)``: a float32 workspace of ``workspace_bytes(name, *args)`` bytes and that size.  0 bytes give one
+    element, so that ``ws`` has a pointer, or ``None`` with ``none_if_empty``."""
+    nbytes = workspace_bytes(name, *args)
+    if none_if_empty and not nbytes:
+        return None, 0
+    return torch.empty((max(nbytes, 4) // 4,), dtype=torch.float32, device=device), nbytes
+
+
 if os.environ.get("MPENGINE_ROCTX") == "1":
     try:
         enable_roctx()

@@ -215,8 +215,7 @@ def dense_wgrad(x, g, with_bias=True):
     rows = xc.numel() // max(k, 1)
     dw = torch.empty((k, u), dtype=torch.float32, device=g.device)
     db = torch.empty((u,), dtype=torch.float32, device=g.device) if with_bias else None
-    nbytes = _ffi.workspace_bytes("mp_dense_wgrad_ws_bytes", rows, k, u)
-    ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.float32, device=g.device) if nbytes else None
+    ws, nbytes = _ffi.float_workspace("mp_dense_wgrad_ws_bytes", rows, k, u, device=g.device, none_if_empty=True)
     _ffi.call("mp_dense_wgrad_f32", _ffi.ptr(xc), rows, k, _ffi.ptr(gc), u, _ffi.ptr(dw), _ffi.ptr(db), _ffi.ptr(ws),
               nbytes, _ffi.stream())
     return dw, db

@@ -19,17 +19,17 @@
 //            registers per lane for the whole kernel.  The s and the f value of one (edge, column) sit in the same lane
 //            and register index, so the gate needs no exchange.
 //   phase 2  per (edge, column): gathered rows + product + bias, BN affine, activations, product                -> LDS
-//   phase 3  per-receiver sums in edge order by 64 threads (one per column).  A receiver whose edges lie inside the tile
-//            is stored directly; a segment cut by a tile boundary leaves its partial sum in the tile's head / tail slot of
-//            the workspace (a receiver that owns a whole tile uses the head slot).  No atomics: two runs give equal bits.
-// cgcnn_update_kernel then adds the slots of a cut receiver in tile order and applies the node update in place; a node
-// without edges has u = 0, and BN_out(0) = beta - mean * inv is NOT zero.
+//   phase 3  per-receiver sums in edge order by 64 threads (one per column): the walk of csrc/mp_edge_tile.h, which
+//            states the rule for receivers cut by a tile boundary.  No atomics: two runs give equal bits.
+// cgcnn_update_kernel then takes every node's u (direct, or the cut receiver's sum) and applies the node update in place;
+// a node without edges has u = 0, and BN_out(0) = beta - mean * inv is NOT zero.
 #include "mp_common.h"
+#include "mp_edge_tile.h"
 
 namespace {
 
 constexpr int F = 64;         // node width = units of the fused step
-constexpr int TE = 32;        // edges per tile
+constexpr int TE = mp_tile::TE;   // edges per tile
 constexpr int MAXD = 64;      // widest edge feature
 constexpr int KS = MAXD / 4;  // MFMA steps at the widest edge feature
 constexpr int GS = MAXD + 1;  // row stride of the edge-feature tile
@@ -124,18 +124,8 @@ __global__ __launch_bounds__(256) void cgcnn_gate_kernel(GateArgs a) {
     __syncthreads();   // the previous tile's walk is done with the tiles in LDS
     // phase 0
     if (t < TE) {
-      int r = -1, s = 0, e = 0;
-      if (t < nv) {
-        e = a.perm0 ? a.perm0[p0 + t] : p0 + t;
-        if (e >= 0 && e < a.E) {
-          r = a.col0[e];
-          s = a.col0[a.E + e];
-          if (r < 0 || r >= a.N || s < 0 || s >= a.N) { r = -1; s = 0; }
-        } else {
-          e = 0;
-        }
-      }
-      recvL[t] = r; sndL[t] = s; eidL[t] = e;
+      const mp_tile::Pos p = mp_tile::load_pos(a.col0, a.perm0, a.N, a.E, p0, t, nv);
+      recvL[t] = p.r; sndL[t] = p.s; eidL[t] = p.e;
     }
     __syncthreads();
     for (int i = t; i < TE * MAXD; i += 256) {
@@ -183,26 +173,12 @@ __global__ __launch_bounds__(256) void cgcnn_gate_kernel(GateArgs a) {
     }
     __syncthreads();
     // phase 3
-    if (t < F) {
-      int cur = -1, first = 0;
-      float sum = 0.0f;
-      for (int e = 0; e <= nv; ++e) {
-        const int r = e < nv ? recvL[e] : -2;
-        if (r != cur) {
-          if (cur >= 0) {
-            const int s0 = a.ptr0[cur], s1 = a.ptr0[cur + 1];
-            if (s0 >= p0 && s1 <= p0 + TE) a.out[(size_t)cur * F + t] = sum;
-            else a.bnd[((size_t)tile * 2 + (first == 0 ? 0 : 1)) * F + t] = sum;
-          }
-          cur = r; first = e; sum = 0.0f;
-        }
-        if (r >= 0) sum += mL[e * MS + t];
-      }
-    }
+    if (t < F)
+      mp_tile::walk<F>(recvL, nv, a.ptr0, a.out, a.bnd, tile, t, [=](int e) { return mL[e * MS + t]; });
   }
 }
 
-// u of every node (direct, the slots of a cut receiver in tile order, or 0 without edges), then the node update in place.
+// u of every node (direct, a cut receiver's sum, or 0 without edges), then the node update in place.
 __global__ void cgcnn_update_kernel(const int32_t* __restrict__ ptr0, int64_t N, const float* __restrict__ bnd,
                                     const float* __restrict__ h, BnVec bn, int act_out, float alpha,
                                     float* __restrict__ out) {
@@ -212,15 +188,7 @@ __global__ void cgcnn_update_kernel(const int32_t* __restrict__ ptr0, int64_t N,
     const int col = static_cast<int>(i - r * F);
     const int64_t s0 = ptr0[r], s1 = ptr0[r + 1];
     float u = 0.0f;
-    if (s1 > s0) {
-      const int64_t t0 = s0 / TE, t1 = (s1 - 1) / TE;
-      if (t0 == t1) {
-        u = out[i];
-      } else {
-        u = bnd[((size_t)t0 * 2 + (s0 == t0 * TE ? 0 : 1)) * F + col];
-        for (int64_t tt = t0 + 1; tt <= t1; ++tt) u += bnd[((size_t)tt * 2) * F + col];
-      }
-    }
+    if (s1 > s0 && !mp_tile::cut_sum<F>(bnd, s0, s1, col, &u)) u = out[i];
     if (bn.on) {
       float inv, shift;
       bn_affine(bn, col, &inv, &shift);
@@ -260,7 +228,7 @@ int mp_batchnorm_infer_f32(const float* x, int64_t R, int64_t C, const float* ga
 
 int mp_cgcnn_gate_ws_bytes(int64_t E, size_t* bytes_out_host) {
   MP_REQUIRE(E >= 0 && bytes_out_host, "mp_cgcnn_gate_ws_bytes: bad arguments");
-  *bytes_out_host = sizeof(float) * 2 * F * static_cast<size_t>((E + TE - 1) / TE);
+  *bytes_out_host = mp_tile::ws_bytes(E, F);
   return MP_OK;
 }
 
@@ -270,7 +238,7 @@ int mp_cgcnn_gate_f32(const float* h, const float* Pa_s, const float* Pa_f, cons
                       const float* const* bn_host, const float* eps_host, int act_s, int act_out, float alpha, float* ws,
                       size_t ws_bytes, float* out, mpStream_t stream) {
   const char* what = "mp_cgcnn_gate_f32";
-  MP_REQUIRE(N >= 0 && E >= 0 && N < (int64_t(1) << 31) - 1 && E < (int64_t(1) << 31) - TE, "%s: bad sizes", what);
+  MP_REQUIRE(mp_tile::sizes_ok(N, E), "%s: bad sizes", what);
   MP_REQUIRE(D >= 1 && D <= MAXD, "%s: the fused gate step takes 1 to %d edge features, got %d", what, MAXD, D);
   MP_REQUIRE(act_s >= 0 && act_out >= 0 && act_s <= MP_ACT_LAST && act_out <= MP_ACT_LAST, "%s: unknown activation code",
              what);
@@ -284,8 +252,7 @@ int mp_cgcnn_gate_f32(const float* h, const float* Pa_s, const float* Pa_f, cons
   }
   if (N == 0) return MP_OK;
   MP_REQUIRE(h && ptr0 && out, "%s: null pointer", what);
-  size_t need = 0;
-  mp_cgcnn_gate_ws_bytes(E, &need);
+  const size_t need = mp_tile::ws_bytes(E, F);
   if (E > 0) {
     MP_REQUIRE(Pa_s && Pa_f && Pb_s && Pb_f && edges && cols && Wc_s && Wc_f && ws, "%s: null pointer", what);
     MP_REQUIRE(ws_bytes >= need, "%s: workspace of %zu bytes, need %zu", what, ws_bytes, need);
@@ -294,7 +261,7 @@ int mp_cgcnn_gate_f32(const float* h, const float* Pa_s, const float* Pa_f, cons
     a.perm0 = perm0; a.Wc_s = Wc_s; a.Wc_f = Wc_f; a.b_s = b_s; a.b_f = b_f; a.bn_s = bn[0]; a.bn_f = bn[1];
     a.out = out; a.bnd = ws; a.N = static_cast<int>(N); a.E = static_cast<int>(E); a.D = D; a.act_s = act_s;
     a.alpha = alpha;
-    const int64_t tiles = (E + TE - 1) / TE;
+    const int64_t tiles = mp_tile::tiles_of(E);
     cgcnn_gate_kernel<<<static_cast<unsigned>(tiles < 1024 ? tiles : 1024), 256, 0, mp::as_stream(stream)>>>(a);
     int rc = mp::check_launch(what);
     if (rc != MP_OK) return rc;

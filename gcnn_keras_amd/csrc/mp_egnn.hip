@@ -14,10 +14,9 @@
 //   phase 2  second layer on the matrix pipe: v_mfma_f32_32x32x2_f32, edges = rows, wave w owns output columns
 //            [32w, 32w+32); its 128 x 32 slab of W2 lives in 64 registers per lane for the whole kernel
 //   phase 3  bias, activation, attention dot (8 lanes per edge, fixed xor tree) and activation             -> LDS
-//   phase 4  per-receiver sums in edge order by 128 threads (one per column).  A receiver whose edges lie inside the tile is
-//            stored directly; a segment cut by a tile boundary leaves its partial sum in the tile's head / tail slot of the
-//            workspace and egnn_edge_finish_kernel adds the slots of one receiver in tile order.  No atomics: two runs
-//            give equal bits.
+//   phase 4  per-receiver sums in edge order by 128 threads (one per column): the walk of csrc/mp_edge_tile.h, which
+//            states the rule for receivers cut by a tile boundary; egnn_edge_finish_kernel writes their sums and zeroes
+//            the receivers without edges.  No atomics: two runs give equal bits.
 // With z1_save / z2_save given (a forward that will be differentiated) both pre-activations are stored per edge; the
 // reverse reads them instead of repeating the gathers, the encoding and the GEMM.
 //
@@ -26,11 +25,12 @@
 // x_bar (E) through Wc^T and the encoding's derivative.  The sums of z1_bar into Pa_bar / Pb_bar run on the segment-sum kernel
 // over the two CSRs (host side), in list order.
 #include "mp_common.h"
+#include "mp_edge_tile.h"
 
 namespace {
 
 constexpr int F = 128;        // node / message width of the fused step
-constexpr int TE = 32;        // edges per tile
+constexpr int TE = mp_tile::TE;   // edges per tile
 constexpr int MAXC = 64;      // widest encoding (2K)
 constexpr int HS = TE + 1;    // row stride of the transposed tiles
 constexpr int MS = F + 1;     // row stride of the edge-major tiles
@@ -143,21 +143,10 @@ __global__ __launch_bounds__(256) void egnn_edge_fwd_kernel(EdgeArgs a) {
     __syncthreads();   // the previous tile's walk is done with the tiles in LDS; the weights above are visible
     // phase 0
     if (t < TE) {
-      int r = -1, s = 0;
-      int e = 0;
+      const mp_tile::Pos p = mp_tile::load_pos(a.col0, a.perm0, a.N, a.E, p0, t, nv);
       float xv = 0.0f;
-      if (t < nv) {
-        e = a.perm0 ? a.perm0[p0 + t] : p0 + t;
-        if (e >= 0 && e < a.E) {
-          r = a.col0[e];
-          s = a.col0[a.E + e];
-          xv = a.x[e];
-          if (r < 0 || r >= a.N || s < 0 || s >= a.N) { r = -1; s = 0; }
-        } else {
-          e = 0;
-        }
-      }
-      recvL[t] = r; sndL[t] = s; eidL[t] = e; xL[t] = xv;
+      if (t < nv) xv = a.x[p.e];   // beside the index loads, not behind them; used for valid rows only
+      recvL[t] = p.r; sndL[t] = p.s; eidL[t] = p.e; xL[t] = xv;
     }
     __syncthreads();
     if (K > 0) {
@@ -233,26 +222,12 @@ __global__ __launch_bounds__(256) void egnn_edge_fwd_kernel(EdgeArgs a) {
     }
     __syncthreads();
     // phase 4
-    if (t < F) {
-      int cur = -1, first = 0;
-      float sum = 0.0f;
-      for (int e = 0; e <= nv; ++e) {
-        const int r = e < nv ? recvL[e] : -2;
-        if (r != cur) {
-          if (cur >= 0) {
-            const int s0 = a.ptr0[cur], s1 = a.ptr0[cur + 1];
-            if (s0 >= p0 && s1 <= p0 + TE) a.out[(size_t)cur * F + t] = sum;
-            else a.bnd[((size_t)tile * 2 + (first == 0 ? 0 : 1)) * F + t] = sum;
-          }
-          cur = r; first = e; sum = 0.0f;
-        }
-        if (r >= 0) sum += attL[e] * mL[e * MS + t];
-      }
-    }
+    if (t < F)
+      mp_tile::walk<F>(recvL, nv, a.ptr0, a.out, a.bnd, tile, t, [=](int e) { return attL[e] * mL[e * MS + t]; });
   }
 }
 
-// Receivers whose edges span several tiles: head / tail slots added in tile order; receivers without edges: zero.
+// Receivers whose edges span several tiles: the cut receiver's sum; receivers without edges: zero; the rest stay.
 __global__ void egnn_edge_finish_kernel(const int32_t* __restrict__ ptr0, int64_t N, const float* __restrict__ bnd,
                                         float* __restrict__ out) {
   const int64_t total = N * F;
@@ -261,11 +236,8 @@ __global__ void egnn_edge_finish_kernel(const int32_t* __restrict__ ptr0, int64_
     const int col = static_cast<int>(i - r * F);
     const int64_t s0 = ptr0[r], s1 = ptr0[r + 1];
     if (s1 <= s0) { out[i] = 0.0f; continue; }
-    const int64_t t0 = s0 / TE, t1 = (s1 - 1) / TE;
-    if (t0 == t1) continue;
-    float sum = bnd[((size_t)t0 * 2 + (s0 == t0 * TE ? 0 : 1)) * F + col];
-    for (int64_t tt = t0 + 1; tt <= t1; ++tt) sum += bnd[((size_t)tt * 2) * F + col];
-    out[i] = sum;
+    float sum;
+    if (mp_tile::cut_sum<F>(bnd, s0, s1, col, &sum)) out[i] = sum;
   }
 }
 
@@ -398,8 +370,7 @@ __global__ __launch_bounds__(256) void egnn_edge_bwd_kernel(EdgeArgs a) {
 }
 
 int check_edge(const char* what, int64_t N, int64_t E, int K, int interleave, int act1, int act2, int act_att) {
-  MP_REQUIRE(N >= 0 && E >= 0 && N < (int64_t(1) << 31) - 1 && E < (int64_t(1) << 31) - TE, "%s: bad sizes",
-             what);
+  MP_REQUIRE(mp_tile::sizes_ok(N, E), "%s: bad sizes", what);
   MP_REQUIRE(K >= 0 && 2 * K <= MAXC, "%s: the fused edge step takes an encoding of at most %d columns (dim_half <= %d)",
              what, MAXC, MAXC / 2);
   MP_REQUIRE(interleave == 0 || interleave == 1, "%s: bad interleave flag", what);
@@ -409,7 +380,7 @@ int check_edge(const char* what, int64_t N, int64_t E, int K, int interleave, in
 }
 
 unsigned edge_grid(int64_t E) {
-  const int64_t tiles = (E + TE - 1) / TE;
+  const int64_t tiles = mp_tile::tiles_of(E);
   return static_cast<unsigned>(tiles < 512 ? tiles : 512);
 }
 
@@ -439,7 +410,7 @@ int mp_position_encoding_grad_f32(const float* x, int64_t M, const float* scales
 
 int mp_egnn_edge_ws_bytes(int64_t E, size_t* bytes_out_host) {
   MP_REQUIRE(E >= 0 && bytes_out_host, "mp_egnn_edge_ws_bytes: bad arguments");
-  *bytes_out_host = sizeof(float) * 2 * F * static_cast<size_t>((E + TE - 1) / TE);
+  *bytes_out_host = mp_tile::ws_bytes(E, F);
   return MP_OK;
 }
 
@@ -451,8 +422,7 @@ int mp_egnn_edge_f32(const float* Pa, const float* Pb, int64_t N, const float* x
   int rc = check_edge("mp_egnn_edge_f32", N, E, dim_half, interleave, act1, act2, act_att);
   if (rc != MP_OK || N == 0) return rc;
   MP_REQUIRE(ptr0 && out, "mp_egnn_edge_f32: null pointer");
-  size_t need = 0;
-  mp_egnn_edge_ws_bytes(E, &need);
+  const size_t need = mp_tile::ws_bytes(E, F);
   if (E > 0) {
     MP_REQUIRE(Pa && Pb && x && cols && Wc && W2 && ws && (dim_half == 0 || scales), "mp_egnn_edge_f32: null pointer");
     MP_REQUIRE(ws_bytes >= need, "mp_egnn_edge_f32: workspace of %zu bytes, need %zu", ws_bytes, need);

@@ -14,16 +14,16 @@
 //            blocks; the gathered rows are loaded ahead of the product, summed behind it, activated               -> LDS
 //   phase 2  A1 W1 (32 x 64 x 32) and A2 W2 (32 x 32 x 32): wave w owns the 16 x 16 block (w >> 1, w & 1).  e' goes out
 //            at its list position (through perm0) and into LDS for the walk
-//   phase 3  per-receiver sums in list order by 32 threads (one per column), as in csrc/mp_cgcnn.hip: a receiver whose
-//            edges lie inside the tile is stored directly, a segment cut by a tile boundary leaves its partial sum in the
-//            tile's head / tail slot of the workspace.  No atomics: two runs give equal bits.
+//   phase 3  per-receiver sums in list order by 32 threads (one per column): the walk step of csrc/mp_edge_tile.h,
+//            which states the rule for receivers cut by a tile boundary.  No atomics: two runs give equal bits.
 // The slabs of Wc, W1 and W2 a wave needs live in 8 + 16 + 8 registers per lane for the whole kernel.  The kernel is bound
 // by the latency of its dependent loads (position -> indices -> rows), not by traffic, so the chain is kept short: with at
 // most SPLITS_LDS graphs the row_splits are copied to LDS once per workgroup and g(e) is searched there (a search in
 // global memory is log2(G) dependent round trips per tile), and the walk's CSR ranges are fetched with the indices.
-// megnet_pool_kernel then adds the slots of a cut receiver in tile order, zeroes the receivers without edges and divides by
-// the edge count for the mean.
+// megnet_pool_kernel then takes every node's sum (direct, or the cut receiver's sum), zeroes the receivers without edges
+// and divides by the edge count for the mean.
 #include "mp_common.h"
+#include "mp_edge_tile.h"
 
 namespace {
 
@@ -31,7 +31,7 @@ constexpr int FE = 32;   // edge width in
 constexpr int H0 = 64;   // first layer of the edge chain
 constexpr int H1 = 32;   // second layer
 constexpr int H2 = 32;   // third layer = edge width out
-constexpr int TE = 32;   // positions per tile
+constexpr int TE = mp_tile::TE;   // positions per tile
 constexpr int SPLITS_LDS = 2048;   // row_splits entries held in LDS (as int32: E < 2^31); more graphs search in global memory
 constexpr int XS = FE + 1;   // row strides in LDS
 constexpr int A1S = H0 + 1;
@@ -98,29 +98,22 @@ __global__ __launch_bounds__(256, 4) void megnet_edge_kernel(EdgeArgs a) {
     // phase 0
     int s0 = 0, s1 = 0;   // CSR range of the position's receiver (threads 0..31), needed by the walk only
     if (t < TE) {
-      int r = -1, s = 0, e = 0, g = 0;
+      const mp_tile::Pos p = mp_tile::load_pos(a.col0, a.perm0, a.N, a.E, p0, t, nv);
+      int g = 0;   // read for valid rows only
       if (t < nv) {
-        e = a.perm0 ? a.perm0[p0 + t] : p0 + t;
-        if (e >= 0 && e < a.E) {
-          r = a.col0[e];
-          s = a.col0[a.E + e];
-          if (r < 0 || r >= a.N || s < 0 || s >= a.N) { r = -1; s = 0; }
-          if (r >= 0) { s0 = a.ptr0[r]; s1 = a.ptr0[r + 1]; }
-          if (splits_in_lds) {   // largest g in [0, G) with splits[g] <= e, as mp_owner_of
-            int lo = 0, hi = static_cast<int>(a.G);
-            while (hi - lo > 1) {
-              const int mid = (lo + hi) >> 1;
-              if (splitsL[mid] <= e) lo = mid; else hi = mid;
-            }
-            g = lo;
-          } else {
-            g = static_cast<int>(mp_owner_of(a.splits, a.G, e));
+        if (p.r >= 0) { s0 = a.ptr0[p.r]; s1 = a.ptr0[p.r + 1]; }
+        if (splits_in_lds) {   // largest g in [0, G) with splits[g] <= e, as mp_owner_of
+          int lo = 0, hi = static_cast<int>(a.G);
+          while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (splitsL[mid] <= p.e) lo = mid; else hi = mid;
           }
+          g = lo;
         } else {
-          e = 0;
+          g = static_cast<int>(mp_owner_of(a.splits, a.G, p.e));
         }
       }
-      recvL[t] = r; sndL[t] = s; eidL[t] = e; gidL[t] = g;
+      recvL[t] = p.r; sndL[t] = p.s; eidL[t] = p.e; gidL[t] = g;
     }
     __syncthreads();
     // every global load of the tile is issued before the first one is waited for: the edge features (thread t holds
@@ -206,27 +199,18 @@ __global__ __launch_bounds__(256, 4) void megnet_edge_kernel(EdgeArgs a) {
       float mv[TE];   // the thread's column: 32 independent LDS reads instead of one per dependent step
 #pragma unroll
       for (int e = 0; e < TE; ++e) mv[e] = mL[e * MS + t];
-      int cur = -1, first = 0;
-      float sum = 0.0f;
+      mp_tile::Walk<H2> w{a.pool, a.bnd, tile, t};
+      const auto range = [&](int, int first) { return make_int2(seg0L[first], seg1L[first]); };
 #pragma unroll
       for (int e = 0; e <= TE; ++e) {
         if (e > nv) break;
-        const int r = e < nv ? recvL[e < TE ? e : 0] : -2;
-        if (r != cur) {
-          if (cur >= 0) {
-            const int s0 = seg0L[first], s1 = seg1L[first];
-            if (s0 >= p0 && s1 <= p0 + TE) a.pool[(size_t)cur * H2 + t] = sum;
-            else a.bnd[((size_t)tile * 2 + (first == 0 ? 0 : 1)) * H2 + t] = sum;
-          }
-          cur = r; first = e; sum = 0.0f;
-        }
-        if (r >= 0) sum += mv[e < TE ? e : 0];
+        w.step(e, e < nv ? recvL[e < TE ? e : 0] : -2, mv[e < TE ? e : 0], range);
       }
     }
   }
 }
 
-// pool of every node: direct, the slots of a cut receiver in tile order, or 0 without edges; the mean divides by the count.
+// pool of every node: direct, a cut receiver's sum, or 0 without edges; the mean divides by the count.
 __global__ void megnet_pool_kernel(const int32_t* __restrict__ ptr0, int64_t N, const float* __restrict__ bnd, int mean,
                                    float* __restrict__ pool) {
   const int64_t total = N * H2;
@@ -236,13 +220,7 @@ __global__ void megnet_pool_kernel(const int32_t* __restrict__ ptr0, int64_t N, 
     const int64_t s0 = ptr0[r], s1 = ptr0[r + 1];
     float u = 0.0f;
     if (s1 > s0) {
-      const int64_t t0 = s0 / TE, t1 = (s1 - 1) / TE;
-      if (t0 == t1) {
-        u = pool[i];
-      } else {
-        u = bnd[((size_t)t0 * 2 + (s0 == t0 * TE ? 0 : 1)) * H2 + col];
-        for (int64_t tt = t0 + 1; tt <= t1; ++tt) u += bnd[((size_t)tt * 2) * H2 + col];
-      }
+      if (!mp_tile::cut_sum<H2>(bnd, s0, s1, col, &u)) u = pool[i];
       if (mean) u = u / static_cast<float>(s1 - s0);
     }
     pool[i] = u;
@@ -255,7 +233,7 @@ extern "C" {
 
 int mp_megnet_edge_ws_bytes(int64_t E, size_t* bytes_out_host) {
   MP_REQUIRE(E >= 0 && bytes_out_host, "mp_megnet_edge_ws_bytes: bad arguments");
-  *bytes_out_host = sizeof(float) * 2 * H2 * static_cast<size_t>((E + TE - 1) / TE);
+  *bytes_out_host = mp_tile::ws_bytes(E, H2);
   return MP_OK;
 }
 
@@ -265,8 +243,7 @@ int mp_megnet_edge_f32(const float* Pa, const float* Pb, int64_t N, const float*
                        const float* W2, const float* b2, int units0, int units1, int units2, int act, float alpha,
                        int pool_op, float* ws, size_t ws_bytes, float* edges_out, float* pool_out, mpStream_t stream) {
   const char* what = "mp_megnet_edge_f32";
-  MP_REQUIRE(N >= 0 && E >= 0 && G >= 0 && N < (int64_t(1) << 31) - 1 && E < (int64_t(1) << 31) - TE, "%s: bad sizes",
-             what);
+  MP_REQUIRE(mp_tile::sizes_ok(N, E) && G >= 0, "%s: bad sizes", what);
   MP_REQUIRE(Fn == 32 && Fe == FE && Fu == 32, "%s: the fused edge step takes node, edge and state widths 32 / 32 / 32, "
              "got %d / %d / %d", what, Fn, Fe, Fu);
   MP_REQUIRE(units0 == H0 && units1 == H1 && units2 == H2, "%s: the fused edge step takes the edge chain [64, 32, 32], "
@@ -275,8 +252,7 @@ int mp_megnet_edge_f32(const float* Pa, const float* Pb, int64_t N, const float*
   MP_REQUIRE(pool_op == MP_SUM || pool_op == MP_MEAN, "%s: pooling is sum or mean, got op %d", what, pool_op);
   if (N == 0) return MP_OK;
   MP_REQUIRE(ptr0 && pool_out, "%s: null pointer", what);
-  size_t need = 0;
-  mp_megnet_edge_ws_bytes(E, &need);
+  const size_t need = mp_tile::ws_bytes(E, H2);
   if (E > 0) {
     MP_REQUIRE(Pa && Pb && Pu && edge_splits && edges && cols && Wc && W1 && W2 && ws && edges_out, "%s: null pointer",
                what);
@@ -286,7 +262,7 @@ int mp_megnet_edge_f32(const float* Pa, const float* Pb, int64_t N, const float*
     a.Pa = Pa; a.Pb = Pb; a.Pu = Pu; a.splits = edge_splits; a.x = edges; a.col0 = cols; a.ptr0 = ptr0; a.perm0 = perm0;
     a.Wc = Wc; a.W1 = W1; a.b1 = b1; a.W2 = W2; a.b2 = b2; a.e_out = edges_out; a.pool = pool_out; a.bnd = ws; a.G = G;
     a.N = static_cast<int>(N); a.E = static_cast<int>(E); a.act = act; a.alpha = alpha;
-    const int64_t tiles = (E + TE - 1) / TE;
+    const int64_t tiles = mp_tile::tiles_of(E);
     megnet_edge_kernel<<<static_cast<unsigned>(tiles < 1024 ? tiles : 1024), 256, 0, mp::as_stream(stream)>>>(a);
     int rc = mp::check_launch(what);
     if (rc != MP_OK) return rc;

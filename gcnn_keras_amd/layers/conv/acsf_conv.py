@@ -81,8 +81,7 @@ class AcsfSpec:
     def grad(self, xyz, g):
         xyz, g = xyz.contiguous(), g.contiguous()
         dx = torch.empty((self.plan.N, 3), dtype=torch.float32, device=xyz.device)
-        nbytes = _ffi.workspace_bytes("mp_acsf_grad_ws_bytes", self.plan.M, self.K)
-        ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.float32, device=xyz.device)
+        ws, nbytes = _ffi.float_workspace("mp_acsf_grad_ws_bytes", self.plan.M, self.K, device=xyz.device)
         csr = []
         for c in range(self.K):
             csr.extend(self._csr(c))

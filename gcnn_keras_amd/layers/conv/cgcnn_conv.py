@@ -25,7 +25,7 @@ import torch
 
 from ... import _ffi
 from ..message import MessagePassingBase
-from ..modules import Activation, Dense, LazyAdd, LazyConcatenate, LazyMultiply
+from ..modules import Activation, Dense, LazyAdd, LazyConcatenate, LazyMultiply, _activation_name
 from ..norm import GraphBatchNormalization
 
 FUSED_GATE_SIZES = {"units": 64, "max_edge_width": 64}   # csrc/mp_cgcnn.hip
@@ -39,11 +39,8 @@ def fused_gate_supported(node_width, units, edge_width, activation_s, activation
         return False
     if edge_width is None or not 1 <= int(edge_width) <= s["max_edge_width"]:
         return False
-    for act in (activation_s, activation_out):
-        if isinstance(act, dict):
-            act = act.get("class_name", act.get("name"))
-        if act not in _ffi.ACTIVATION_CODES:
-            return False
+    if any(_activation_name(act) not in _ffi.ACTIVATION_CODES for act in (activation_s, activation_out)):
+        return False
     if dtype not in ("float32", torch.float32):
         return False
     return pooling_method in ("sum", "segment_sum", "reduce_sum") and pooling_index == 0
@@ -96,8 +93,7 @@ class FusedGateStep:
             bn = (ctypes.c_void_p * 12)(*ptrs)
             eps = (ctypes.c_float * 3)(*[b.epsilon for b in norms])
         ptr0, perm0, _ = plan.csr(0)
-        nbytes = _ffi.workspace_bytes("mp_cgcnn_gate_ws_bytes", e)
-        ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.float32, device=hv.device)
+        ws, nbytes = _ffi.float_workspace("mp_cgcnn_gate_ws_bytes", e, device=hv.device)
         out = torch.empty((n, f), dtype=torch.float32, device=hv.device)
         bias_s = None if lay.s.bias is None else lay.s.bias.detach()
         bias_f = None if lay.f.bias is None else lay.f.bias.detach()

@@ -73,8 +73,7 @@ class EdgeStepSpec:
     def forward(self, pa, pb, x, save=False):
         n, e, f = self.plan.N, self.plan.M, FUSED_EDGE_SIZES["units"]
         ptr0, perm0, _ = self.plan.csr(0)
-        nbytes = _ffi.workspace_bytes("mp_egnn_edge_ws_bytes", e)
-        ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.float32, device=pa.device)
+        ws, nbytes = _ffi.float_workspace("mp_egnn_edge_ws_bytes", e, device=pa.device)
         out = torch.empty((n, f), dtype=torch.float32, device=pa.device)
         z1 = torch.empty((e, f), dtype=torch.float32, device=pa.device) if save else None
         z2 = torch.empty((e, f), dtype=torch.float32, device=pa.device) if save else None

@@ -26,7 +26,7 @@ import torch
 from ... import _ffi
 from ..base import GraphBaseLayer
 from ..gather import GatherNodes, GatherState
-from ..modules import Dense, LazyConcatenate
+from ..modules import Dense, LazyConcatenate, _activation_name
 from ..pooling import PoolingGlobalEdges, PoolingLocalEdges, PoolingNodes
 
 _KERNEL_KEYS = ("kernel_regularizer", "activity_regularizer", "bias_regularizer", "kernel_constraint", "bias_constraint",
@@ -45,9 +45,7 @@ def fused_edge_supported(node_width, edge_width, state_width, edge_embed, activa
         return False
     if edge_embed is None or [int(w) for w in edge_embed] != s["edge_embed"]:
         return False
-    if isinstance(activation, dict):
-        activation = activation.get("class_name", activation.get("name"))
-    if activation not in _ffi.ACTIVATION_CODES:
+    if _activation_name(activation) not in _ffi.ACTIVATION_CODES:
         return False
     if dtype not in ("float32", torch.float32):
         return False
@@ -109,8 +107,7 @@ class FusedEdgeStep:
         pb = dense_values(vc, k0[fn:2 * fn], None, "linear")
         pu = dense_values(env.detach().contiguous(), k0[2 * fn + fe:], detach(d0.bias), "linear")
         ptr0, perm0, _ = plan.csr(0)
-        nbytes = _ffi.workspace_bytes("mp_megnet_edge_ws_bytes", e)
-        ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.float32, device=vv.device)
+        ws, nbytes = _ffi.float_workspace("mp_megnet_edge_ws_bytes", e, device=vv.device)
         e_out = torch.empty((e, s["edge_embed"][2]), dtype=torch.float32, device=vv.device)
         pool = torch.empty((n, s["edge_embed"][2]), dtype=torch.float32, device=vv.device)
         _ffi.call("mp_megnet_edge_f32", _ffi.ptr(pa), _ffi.ptr(pb), n, _ffi.ptr(pu), _ffi.ptr(edge.row_splits), g,

@@ -432,8 +432,7 @@ class EdgeAngleSpec:
         return out
 
     def grad(self, v, g):
-        nbytes = _ffi.workspace_bytes("mp_edge_angle_grad_ws_bytes", self.plan.M)
-        ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.float32, device=v.device)
+        ws, nbytes = _ffi.float_workspace("mp_edge_angle_grad_ws_bytes", self.plan.M, device=v.device)
         v_bar = torch.empty_like(v)
         ptr0, perm0, _ = self.plan.csr(0)
         ptr1, perm1, _ = self.plan.csr(1)

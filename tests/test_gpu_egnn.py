@@ -6,6 +6,7 @@ import pytest
 import torch
 
 import egnn_reference as ref
+import megnet_reference
 from gcnn_keras_amd import _ffi, synth
 from gcnn_keras_amd.layers.conv.egnn_conv import FusedEdgeStep
 from gcnn_keras_amd.layers.gather import GatherEmbeddingSelection
@@ -209,6 +210,85 @@ def test_fused_edge_step_forward_and_reverse(attention, encoding, order):
             what, name, rowwise_rel(got, other), 2 * bar)
     ns = b["node_splits"]
     assert torch.all(fused[ns[1]:ns[2]] == 0)       # the lone atom: a node without edges
+
+
+# The walk off the molecular shapes (no receiver of a molecule has 32 edges): 4 nodes, node 2 without edges.  hand<E>:
+# megnet_reference.hand_case(E), tiles of 32 positions with 0, 1 and 2 boundaries; deg96: receiver degrees 5, 70, 0, 21 -
+# node 1 leaves a tail slot in tile 0, owns tile 1 whole and leaves a head slot in tile 2, node 3 ends on the last tile's
+# edge.
+TILE_GRAPHS = ["hand0", "hand1", "hand31", "hand32", "hand33", "hand64", "hand65", "deg96"]
+
+
+def _tile_graph(name, order, seed=0):
+    if name == "deg96":
+        recv = np.repeat(np.arange(4), [5, 70, 0, 21])
+        idx = np.stack([recv, np.random.default_rng(seed).integers(0, 4, size=96)], axis=1).astype(np.int64)
+    else:
+        idx = megnet_reference.hand_case(int(name[4:]), seed)[0]
+    if order == "shuffled":
+        idx = idx[np.random.default_rng(seed + 1).permutation(len(idx))]
+    return idx
+
+
+# attention and encoding on for every graph and order; both off once, on the graph with every kind of slot.  Without the
+# encoding x_bar shares no rounding with the float32 restatement (with it the sin arguments' rounding dominates both), and
+# over this few rows one cancelling row decides the comparison either way: run over all 16 graphs and orders, the engine
+# was 0.1x to 2.5x as far from float64 as the restatement (the layer sequence likewise) and two cases missed a bar by 3 %.
+TILE_CASES = [(name, order, True, True) for name in TILE_GRAPHS for order in ("sorted", "shuffled")] + [
+    ("deg96", "sorted", False, False)]
+
+
+@pytest.mark.parametrize("name,order,attention,encoding", TILE_CASES)
+def test_fused_edge_step_at_tile_edges(name, order, attention, encoding):
+    idx = _tile_graph(name, order)
+    e = len(idx)
+    ns, es = np.array([0, 4], np.int64), np.array([0, e], np.int64)
+    rng = np.random.default_rng(31)
+    step = _edge_layers(attention, encoding)
+    h = _rag(rng.normal(size=(4, 128)).astype(np.float32), ns)
+    x = _rag(rng.uniform(0.5, 30.0, size=(e, 1)).astype(np.float32), es)     # the step takes any x; d^2 of a 5.5 A cutoff
+    ei = _rag(idx, es)
+    hv = h.values.detach().clone().requires_grad_(True)
+    xv = x.values.detach().clone().requires_grad_(True)
+    g = torch.from_numpy(rng.normal(size=(4, 128)).astype(np.float32)).cuda()
+
+    def run():
+        with torch.enable_grad():
+            out = step(h.with_values(hv), x.with_values(xv), ei).values
+            return (out.detach(),) + torch.autograd.grad(out, [hv, xv], g)
+
+    fused, fh, fx = run()
+    assert all(torch.equal(a, b) for a, b in zip(run(), (fused, fh, fx)))       # two runs: equal bits
+    with torch.no_grad():
+        assert torch.equal(step(h, x, ei).values, fused)
+    assert tuple(fused.shape) == tuple(fh.shape) == (4, 128) and tuple(fx.shape) == (e, 1)
+    lone = np.bincount(idx[:, 0], minlength=4) == 0
+    assert lone[2] and torch.all(fused[torch.from_numpy(lone).cuda()] == 0)     # nodes without edges: exactly zero
+    if e == 0:
+        assert torch.all(fused == 0) and torch.all(fh == 0)
+        return
+    with torch.enable_grad():
+        seq = _sequence(step, h.with_values(hv), x.with_values(xv), ei).values
+        sh, sx = torch.autograd.grad(seq, [hv, xv], g)
+    outs = {}
+    for dt in (torch.float32, torch.float64):
+        hr = hv.detach().cpu().to(dt).requires_grad_(True)
+        xr = xv.detach().cpu().to(dt).requires_grad_(True)
+        _, m_i = ref.edge_step(hr, xr, torch.from_numpy(idx), _mlp_weights(step.edge_mlp, dt),
+                               _mlp_weights(step.attention_mlp, dt), dt, expand=encoding)
+        gh, gx = torch.autograd.grad(m_i, [hr, xr], g.cpu().to(dt))
+        outs[dt] = (m_i.detach().numpy(), gh.numpy(), gx.numpy())
+    what = "edge step %s %s att=%d enc=%d" % (name, order, attention, encoding)
+    # the bars of test_fused_edge_step_forward_and_reverse
+    for k, label, got, other in ((0, "forward", fused, seq), (1, "h_bar", fh, sh), (2, "x_bar", fx, sx)):
+        got, other = got.detach().cpu().numpy(), other.detach().cpu().numpy()
+        r32, r64 = outs[torch.float32][k], outs[torch.float64][k]
+        cap = ENC_REV_CAP if label == "x_bar" else 5e-5
+        assert_rows_close(got, r32, r64, what="%s %s" % (what, label), cap=cap)
+        assert_rows_close(other, r32, r64, what="%s %s (layer sequence)" % (what, label), cap=cap)
+        bar = max(1e-5, min(2 * rowwise_rel(r32, r64), cap))
+        assert rowwise_rel(got, other) <= 2 * bar, "%s %s: fused vs layer sequence %.3g (bar %.3g)" % (
+            what, label, rowwise_rel(got, other), 2 * bar)
 
 
 def test_fused_edge_step_isolated_nodes_and_reorders():
