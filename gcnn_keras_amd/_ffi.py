@@ -27,6 +27,7 @@ MP_SCALER_MAX_NUMBER, MP_SCALER_CHUNK_ROWS, MP_SCALER_MAX_STATES = 95, 256, 32  
 MP_PERIODIC_MAX_HITS, MP_PERIODIC_MAX_IMAGE, MP_PERIODIC_MAX_CANDIDATES = 1024, 511, 1048576
 MP_PERIODIC_FLAG_CAPACITY, MP_PERIODIC_FLAG_IMAGE_RANGE, MP_PERIODIC_FLAG_SINGULAR = 1, 2, 4
 MP_CMPNN_EDGE_TILE, MP_GRU_RAGGED_MAX_UNITS = 64, 512   # include/mpengine.h
+MP_GAT_V1, MP_GAT_V2, MP_GAT_MAX_HEADS = 0, 1, 8   # include/mpengine.h
 
 ACTIVATION_CODES = {
     None: 0, "linear": 0, "relu": 1, "kgcnn>shifted_softplus": 2, "shifted_softplus": 2, "softplus": 3,
@@ -62,6 +63,8 @@ _SIGNATURES = {
                                          c_float, P, P],
     "mp_pool_graph_f32": [c_int, P, P, c_int64, c_int64, P, P, P],
     "mp_segment_softmax_csr_f32": [P, c_int64, c_int64, P, P, c_int64, P, P],
+    "mp_segment_softmax_csr_grad_f32": [P, P, c_int64, c_int64, P, P, c_int64, P, P],
+    "mp_segment_weight_grad_f32": [P, P, c_int64, c_int64, P, c_int64, P, P],
     "mp_scatter_relational_f32": [c_int, P, c_int64, c_int64, P, P, c_int64, c_int64, P, P],
     "mp_dense_f32": [P, c_int64, c_int64, P, P, c_int64, c_int, c_float, P, P],
     "mp_dense_ex_f32": [P, c_int64, c_int64, P, P, c_int64, c_int, c_float, c_int, c_int, c_float, P, P, P, P, P, P],
@@ -198,6 +201,10 @@ _SIGNATURES = {
                               c_float, P, P, P],
     "mp_frac_to_real_f32": [P, P, P, c_int64, c_int64, c_int, P, P],
     "mp_batchnorm_infer_f32": [P, c_int64, c_int64, P, P, P, P, c_float, P, P],
+    "mp_gat_node_scores_f32": [c_int, c_int, P, P, c_int64, P, P],
+    "mp_gat_logits_f32": [c_int, c_int, c_int, P, P, P, P, P, P, c_int64, P, c_int, P, c_int64, P, c_int, c_float, P,
+                          c_int64, c_int64, P],
+    "mp_gat_attend_f32": [c_int, c_int, P, c_int64, P, c_int64, c_int64, P, c_int64, P, P, P, P],
     "mp_cgcnn_gate_ws_bytes": [c_int64, P],
     "mp_cgcnn_gate_f32": [P, P, P, P, P, c_int64, P, c_int, P, c_int64, P, P, P, P, P, P, P, P, c_int, c_int, c_float, P,
                           c_size_t, P, P],

@@ -161,6 +161,60 @@ class SegmentSumAdjoint(torch.autograd.Function):
         return (SegmentSum.apply(h.contiguous(), *ctx.args),) + (None,) * 6
 
 
+class WeightedSegmentSum(torch.autograd.Function):
+    """CSR segment sum ``out[n] = sum_e w_e data[e]`` with a differentiable weight (attention pooling): the data gradient
+    is ``SegmentSum``'s adjoint, the weight gradient ``w_bar_e = g[seg(e)] . data[e]`` (mp_segment_weight_grad_f32).
+    First order."""
+
+    @staticmethod
+    def forward(ctx, data, weight, ptr, perm, n_out, seg_ids):
+        from .ops.segment import _segment_reduce_raw
+        ctx.ptr, ctx.n_out, ctx.seg_ids = ptr, n_out, seg_ids
+        ctx.save_for_backward(data, weight)
+        return _segment_reduce_raw(_ffi.MP_SUM, data, ptr, perm, n_out, weight, False)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        data, weight = ctx.saved_tensors
+        gc = g.contiguous()
+        d_bar = w_bar = None
+        if ctx.needs_input_grad[0]:
+            d_bar = _segment_sum_adjoint(gc, _ffi.MP_SUM, ctx.ptr, ctx.n_out, weight, ctx.seg_ids)
+        if ctx.needs_input_grad[1]:
+            dc = data.contiguous()
+            m, elems = _rows_elems(dc)
+            w_bar = torch.empty(tuple(weight.shape), dtype=torch.float32, device=gc.device)
+            _ffi.call("mp_segment_weight_grad_f32", _ffi.ptr(gc), _ffi.ptr(dc), m, elems,
+                      _ffi.ptr(ctx.seg_ids.contiguous()), ctx.n_out, _ffi.ptr(w_bar), _ffi.stream())
+        return d_bar, w_bar, None, None, None, None
+
+
+class SegmentSoftmax(torch.autograd.Function):
+    """``segment_softmax`` over CSR segments; backward ``y (g - sum_seg y g)`` (mp_segment_softmax_csr_grad_f32).
+    First order."""
+
+    @staticmethod
+    def forward(ctx, data, ptr, perm, n_seg):
+        from .ops.segment import _segment_softmax_raw
+        y = _segment_softmax_raw(data, ptr, perm, n_seg)
+        ctx.ptr, ctx.perm, ctx.n_seg = ptr, perm, n_seg
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        y, = ctx.saved_tensors
+        gc = g.contiguous()
+        m, elems = _rows_elems(y)
+        # rows outside every segment keep the zero: the softmax does not write them either
+        out = torch.zeros_like(y)
+        _ffi.call("mp_segment_softmax_csr_grad_f32", _ffi.ptr(y), _ffi.ptr(gc), m, elems, _ffi.ptr(ctx.ptr),
+                  _ffi.ptr(ctx.perm), ctx.n_seg, _ffi.ptr(out), _ffi.stream())
+        return out, None, None, None
+
+
 class PoolGraph(torch.autograd.Function):
     """Per-graph sum / mean; backward repeats the graph row over its nodes (GatherState kernel)."""
 

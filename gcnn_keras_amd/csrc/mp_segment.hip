@@ -168,6 +168,47 @@ __global__ void segment_softmax_csr_kernel(const float* __restrict__ a, int64_t 
   }
 }
 
+// Reverse of segment_softmax: out_e = y_e (g_e - sum_{e' in seg} y_e' g_e'), the inner sum in list order; one work item
+// per (segment, feature) like the forward.
+__global__ void segment_softmax_csr_grad_kernel(const float* __restrict__ y, const float* __restrict__ g, int64_t M,
+                                                int64_t row_elems, const int32_t* __restrict__ ptr,
+                                                const int32_t* __restrict__ perm, int64_t n_seg, float* __restrict__ out) {
+  const int64_t total = n_seg * row_elems;
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
+  for (int64_t t = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; t < total; t += stride) {
+    const int64_t c = t % row_elems;
+    const int64_t n = t / row_elems;
+    int64_t lo = static_cast<int64_t>(ptr[n]);
+    int64_t hi = static_cast<int64_t>(ptr[n + 1]);
+    lo = lo < 0 ? 0 : (lo > M ? M : lo);
+    hi = hi < lo ? lo : (hi > M ? M : hi);
+    float dot = 0.0f;
+    for (int64_t e = lo; e < hi; ++e) {
+      const int64_t r = perm ? static_cast<int64_t>(perm[e]) : e;
+      if (r >= 0 && r < M) dot += y[r * row_elems + c] * g[r * row_elems + c];
+    }
+    for (int64_t e = lo; e < hi; ++e) {
+      const int64_t r = perm ? static_cast<int64_t>(perm[e]) : e;
+      if (r >= 0 && r < M) out[r * row_elems + c] = y[r * row_elems + c] * (g[r * row_elems + c] - dot);
+    }
+  }
+}
+
+// Weight gradient of the weighted segment sum out[n] = sum_e w_e data[e]: w_bar_e = sum_c g[seg(e), c] data[e, c] in
+// column order, one work item per row; a row whose segment id lies outside [0, N) gets 0.
+__global__ void segment_weight_grad_kernel(const float* __restrict__ g, const float* __restrict__ data, int64_t M,
+                                           int64_t row_elems, const int32_t* __restrict__ seg_ids, int64_t N,
+                                           float* __restrict__ out) {
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
+  for (int64_t e = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; e < M; e += stride) {
+    const int64_t n = seg_ids[e];
+    float dot = 0.0f;
+    if (n >= 0 && n < N)
+      for (int64_t c = 0; c < row_elems; ++c) dot += g[n * row_elems + c] * data[e * row_elems + c];
+    out[e] = dot;
+  }
+}
+
 __device__ __forceinline__ void atomic_max_f32(float* addr, float v) {
   // ordered-int trick: valid for all non-NaN floats.  The branch goes by the sign BIT: -0.0 compares >= 0 but its pattern
   // is INT_MIN, which as a signed-int operand loses every max and wins every min (a -0.0 update erased a slot's minimum).
@@ -285,6 +326,25 @@ int mp_segment_softmax_csr_f32(const float* a, int64_t M, int64_t row_elems, con
   segment_softmax_csr_kernel<int32_t><<<mp::grid_for(N * row_elems), 256, 0, mp::as_stream(stream)>>>(
       a, M, row_elems, ptr, perm, N, out);
   return mp::check_launch("mp_segment_softmax_csr_f32");
+}
+
+int mp_segment_softmax_csr_grad_f32(const float* y, const float* g, int64_t M, int64_t row_elems, const int32_t* ptr,
+                                    const int32_t* perm, int64_t N, float* out, mpStream_t stream) {
+  MP_REQUIRE(M >= 0 && N >= 0 && row_elems >= 1, "mp_segment_softmax_csr_grad_f32: bad sizes");
+  if (M == 0 || N == 0) return MP_OK;
+  MP_REQUIRE(y && g && ptr && out, "mp_segment_softmax_csr_grad_f32: null pointer");
+  segment_softmax_csr_grad_kernel<<<mp::grid_for(N * row_elems), 256, 0, mp::as_stream(stream)>>>(y, g, M, row_elems, ptr,
+                                                                                                 perm, N, out);
+  return mp::check_launch("mp_segment_softmax_csr_grad_f32");
+}
+
+int mp_segment_weight_grad_f32(const float* g, const float* data, int64_t M, int64_t row_elems, const int32_t* seg_ids,
+                               int64_t N, float* out, mpStream_t stream) {
+  MP_REQUIRE(M >= 0 && N >= 0 && row_elems >= 1, "mp_segment_weight_grad_f32: bad sizes");
+  if (M == 0) return MP_OK;
+  MP_REQUIRE(data && seg_ids && out && (g || N == 0), "mp_segment_weight_grad_f32: null pointer");
+  segment_weight_grad_kernel<<<mp::grid_for(M), 256, 0, mp::as_stream(stream)>>>(g, data, M, row_elems, seg_ids, N, out);
+  return mp::check_launch("mp_segment_weight_grad_f32");
 }
 
 int mp_scatter_relational_f32(int op, const float* edges, int64_t M, int64_t row_elems, const int32_t* recv,

@@ -159,7 +159,11 @@ PoolingWeightedGlobalEdges = PoolingWeightedEmbedding
 
 
 class PoolingLocalEdgesAttention(GraphBaseLayer):
-    r"""Attention pooling ``n_i = sum_j softmax_j(a_ij) e_ij`` (kgcnn/layers/pooling.py:464-546)."""
+    r"""Attention pooling ``n_i = sum_j softmax_j(a_ij) e_ij`` (kgcnn/layers/pooling.py:464-546).  Under grad the softmax
+    and the weighted sum record ``autograd.SegmentSoftmax`` / ``WeightedSegmentSum`` (gradients of the edges and of the
+    attention logits); without a tape the two calls are the plain kernels."""
+
+    weight_gradients = True   # layers/base.py: no weight of this layer is left off the tape
 
     def __init__(self, pooling_index=0, **kwargs):
         super().__init__(**kwargs)
@@ -175,7 +179,8 @@ class PoolingLocalEdgesAttention(GraphBaseLayer):
         n_out = plan.N
         if not self.has_unconnected:
             n_out = int(seg[-1].item()) + 1 if plan.M > 0 else 0
-        out = segment_reduce_csr(_ffi.MP_SUM, edges.values, ptr, perm, n_out, weight=ats)
+        out = segment_reduce_csr(_ffi.MP_SUM, edges.values, ptr, perm, n_out, weight=ats,
+                                 seg_ids=plan.col(self.pooling_index))
         return nodes.with_values(out)
 
     def get_config(self):

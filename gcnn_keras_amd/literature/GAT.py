@@ -1,10 +1,15 @@
-"""GAT model builder (mirror of kgcnn/literature/GAT.py:20-123, ``make_model``) on the engine's attention heads."""
+"""GAT model builder (mirror of kgcnn/literature/GAT.py:20-123, ``make_model``) on the engine's attention heads.
+
+Each block's heads are handed to one ``FusedAttentionBlock`` (layers/conv/gat_conv.py): where the sizes fit
+(``model.fused_attention_blocks``) the block runs on csrc/mp_gat.hip, three node-side Dense launches per head plus two
+launches for all heads; every other configuration, every call on a tape (training) and ``model.use_fused_attention =
+False`` take the layer sequence, one engine call per Keras layer."""
 from ..layers.casting import ChangeTensorType
-from ..layers.conv.gat_conv import AttentionHeadGAT
+from ..layers.conv.gat_conv import AttentionHeadGAT, FusedAttentionBlock
 from ..layers.mlp import MLP, GraphMLP
 from ..layers.modules import Activation, Dense, LazyAverage, LazyConcatenate, OptionalInputEmbedding
 from ..layers.pooling import PoolingNodes
-from ..model.utils import Model, update_model_kwargs
+from ..model.utils import RouteSwitchModel, update_model_kwargs
 
 __model_version__ = "2022.11.25"
 
@@ -26,6 +31,14 @@ model_default = {
 }
 
 
+class _GatModel(RouteSwitchModel):
+    """``Model`` with the ``use_fused_attention`` switch over all heads."""
+
+    switch_attr, switch_layers_attr = "use_fused_attention", "attention_heads"
+    attention_heads = ()
+    use_fused_attention = RouteSwitchModel.switch
+
+
 def _feature_width(spec, embedding):
     return embedding["output_dim"] if len(spec["shape"]) < 2 else spec["shape"][-1]
 
@@ -38,7 +51,8 @@ def make_model(inputs: list = None, input_embedding: dict = None, attention_args
                head_class=AttentionHeadGAT):
     r"""Build GAT (kgcnn/literature/GAT.py:89-121).  Model inputs ``[node_attributes, edge_attributes, edge_indices]``;
     per block ``attention_heads_num`` heads are concatenated or averaged (then activated).  ``head_class`` lets the
-    GATv2 builder reuse this wiring."""
+    GATv2 builder reuse this wiring.  ``model.fused_attention_blocks`` lists which blocks fit the fused kernels;
+    ``model.attention_heads[i].use_fused_attention`` / ``model.use_fused_attention`` switch the route."""
     if output_embedding not in ("graph", "node"):
         raise ValueError("Unsupported output embedding for `GAT`")
     embed_n = OptionalInputEmbedding(**input_embedding["node"], use_embedding=len(inputs[0]["shape"]) < 2)
@@ -46,6 +60,7 @@ def make_model(inputs: list = None, input_embedding: dict = None, attention_args
     units = attention_args["units"]
     dense0 = Dense(units=units, activation="linear")
     heads = [[head_class(**attention_args) for _ in range(attention_heads_num)] for _ in range(depth)]
+    blocks = [FusedAttentionBlock(block) for block in heads]
     combine = LazyConcatenate(axis=-1) if attention_heads_concat else LazyAverage()
     head_act = None if attention_heads_concat else Activation(activation=attention_args["activation"])
     pool = PoolingNodes(**pooling_nodes_args) if output_embedding == "graph" else None
@@ -57,8 +72,16 @@ def make_model(inputs: list = None, input_embedding: dict = None, attention_args
         node_input, edge_input, edi = model_inputs
         nk = dense0(embed_n(node_input))
         ed = embed_e(edge_input)
-        for block in heads:
-            nk = combine([head([nk, ed, edi]) for head in block])
+        for block, fused in zip(heads, blocks):
+            if fused.route(nk, ed, None):
+                stacked, _ = fused(nk, ed, edi)
+                n, k, u = stacked.shape
+                if attention_heads_concat:      # the concatenated heads are the tensor itself
+                    nk = nk.with_values(stacked.view(n, k * u))
+                else:
+                    nk = combine([nk.with_values(stacked[:, i]) for i in range(k)])
+            else:
+                nk = combine([head([nk, ed, edi]) for head in block])
             if head_act is not None:
                 nk = head_act(nk)
         if output_embedding == "graph":
@@ -74,25 +97,18 @@ def make_model(inputs: list = None, input_embedding: dict = None, attention_args
     width = units
     for block in heads:
         for head in block:
+            # the head's build creates its Dense weights for these widths (layers/conv/gat_conv.py)
             head.ensure_built([(None, None, width), (None, None, edge_width), (None, None, 2)])
-            _build_head(head, width, edge_width)
         width = units * attention_heads_num if attention_heads_concat else units
     out_mlp.ensure_built((None, width) if output_embedding == "graph" else (None, None, width))
     flat_heads = [head for block in heads for head in block]
-    model = Model(name, forward, [embed_n, embed_e, dense0] + flat_heads + [out_mlp],
-                  config={"depth": depth, "attention_args": attention_args, "attention_heads_num": attention_heads_num})
+    model = _GatModel(name, forward, [embed_n, embed_e, dense0] + flat_heads + [out_mlp],
+                      config={"depth": depth, "attention_args": attention_args,
+                              "attention_heads_num": attention_heads_num})
     model.__kgcnn_model_version__ = __model_version__
-    model.auto_graph = True   # re-bound inputs replay the whole layer sequence from one HIP graph (model/utils.py)
+    model.attention_heads = flat_heads
+    model.attention_blocks = blocks
+    model.fused_attention_blocks = [bool(fused.supported(edge_width)) for fused in blocks]
+    model.auto_graph = True   # re-bound inputs replay the whole call sequence from one HIP graph (model/utils.py)
     return model
 
-
-def _build_head(head, node_width, edge_width):
-    """Create the head's weights for known input widths (the layers build lazily otherwise)."""
-    units = head.units
-    head.lay_linear_trafo.ensure_built((None, None, node_width))
-    edge_part = edge_width if head.use_edge_features else 0
-    if hasattr(head, "lay_alpha_activation"):      # GATv2: logits from the raw node features
-        head.lay_alpha_activation.ensure_built((None, None, 2 * node_width + edge_part))
-        head.lay_alpha.ensure_built((None, None, units))
-    else:
-        head.lay_alpha.ensure_built((None, None, 2 * units + edge_part))

@@ -77,6 +77,16 @@ def categorical_crossentropy(y_pred, y_true, sample_weight=None):
     return _reduce(-(t * p.log()).sum(dim=-1), sample_weight)
 
 
+def binary_crossentropy(y_pred, y_true, sample_weight=None):
+    """Keras ``binary_crossentropy`` on probabilities (``from_logits=False``, tf.keras.backend.binary_crossentropy): p
+    clipped to [eps, 1 - eps], ``-(y log(p + eps) + (1 - y) log(1 - p + eps))``, mean over the last axis."""
+    p = _values(y_pred)
+    t = _values(y_true, p).to(p.dtype).reshape(p.shape)
+    p = p.clamp(_EPS, 1.0 - _EPS)
+    bce = t * torch.log(p + _EPS) + (1.0 - t) * torch.log(1.0 - p + _EPS)
+    return _reduce(-bce.mean(dim=-1), sample_weight)
+
+
 def flat_target(target, like, row_splits_host):
     """A per-atom target as the flat ``(N, ...)`` values of ``like`` (the model's flat output): a ``RaggedTensor`` gives
     its values, a flat array is taken as it is, a padded ``(B, Nmax, ...)`` array (one axis more than ``like``) is
@@ -99,7 +109,7 @@ def flat_target(target, like, row_splits_host):
 
 _LOSSES = {"mean_absolute_error": mean_absolute_error, "mae": mean_absolute_error,
            "mean_squared_error": mean_squared_error, "mse": mean_squared_error,
-           "categorical_crossentropy": categorical_crossentropy}
+           "categorical_crossentropy": categorical_crossentropy, "binary_crossentropy": binary_crossentropy}
 
 
 def get_loss(name):

@@ -252,7 +252,7 @@ class Model:
     def compile(self, optimizer="adam", loss="mean_absolute_error", clipnorm=None):
         """``optimizer``: a ``torch.optim.Optimizer`` over ``trainable_weights``, or ``"adam"`` / ``"sgd"`` with Keras'
         defaults (Adam lr 1e-3, betas (0.9, 0.999), epsilon 1e-7; SGD lr 0.01).  ``loss``: ``"mean_absolute_error"``,
-        ``"mean_squared_error"`` or ``"categorical_crossentropy"`` (Keras semantics, reduction sum over batch size).
+        ``"mean_squared_error"``, ``"categorical_crossentropy"`` or ``"binary_crossentropy"`` (Keras semantics, reduction sum over batch size).
         ``clipnorm``: clip every gradient tensor to this L2 norm before the step (Keras OptimizerV2 ``clipnorm``)."""
         from .losses import get_loss
         loss_fn = get_loss(loss)

@@ -36,8 +36,13 @@ def csr_from_sorted_ids(segment_ids, num_segments):
 
 def segment_reduce_csr(op, data, ptr, perm, n_out, weight=None, normalize_by_weight=False, seg_ids=None):
     """out[n] = op over rows [ptr[n], ptr[n+1]) of ``data`` (through ``perm`` if given); rows without members are 0.
-    ``seg_ids`` (segment id per row, original order) is only needed when a gradient w.r.t. ``data`` is requested."""
-    from ..autograd import SegmentSum, needs_grad
+    ``seg_ids`` (segment id per row, original order) is only needed when a gradient w.r.t. ``data`` or ``weight`` is
+    requested."""
+    from ..autograd import SegmentSum, WeightedSegmentSum, needs_grad
+    if needs_grad(weight):
+        if seg_ids is None or normalize_by_weight or op != _ffi.MP_SUM:
+            raise NotImplementedError("the weight gradient needs the segment ids, sum pooling and no weight normalisation")
+        return WeightedSegmentSum.apply(data, weight, ptr, perm, n_out, seg_ids)
     if needs_grad(data):
         if seg_ids is None or normalize_by_weight:
             raise NotImplementedError("gradient needs the segment ids and no weight normalisation")
@@ -67,6 +72,13 @@ def segment_ops_by_name(segment_name: str, data, segment_ids):
 
 
 def segment_softmax_csr(data, ptr, perm, n_seg):
+    from ..autograd import SegmentSoftmax, needs_grad
+    if needs_grad(data):
+        return SegmentSoftmax.apply(data, ptr, perm, n_seg)
+    return _segment_softmax_raw(data, ptr, perm, n_seg)
+
+
+def _segment_softmax_raw(data, ptr, perm, n_seg):
     flat, m, elems = _flat2d(data)
     out = torch.empty_like(flat)
     _ffi.call("mp_segment_softmax_csr_f32", _ffi.ptr(flat), m, elems, _ffi.ptr(ptr), _ffi.ptr(perm), n_seg,

@@ -1,0 +1,224 @@
+"""GAT / GATv2 on the fused attention kernels: the configuration rule, the unchanged configs, the new ABI symbols, the
+binary cross-entropy and the restatement the GPU tests measure against.  Runs without a GPU."""
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import gat_reference as gref
+from gcnn_keras_amd import _ffi
+from gcnn_keras_amd.layers.conv import gat_conv
+from gcnn_keras_amd.model import losses
+from oracle import kgcnn_oracle as ko
+from parity import BAR_CAP, max_rel, rowwise_rel
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW_SYMBOLS = ("mp_gat_logits_f32", "mp_gat_attend_f32", "mp_gat_node_scores_f32", "mp_segment_softmax_csr_grad_f32",
+               "mp_segment_weight_grad_f32")
+
+
+def test_served_sizes():
+    assert gat_conv.FUSED_ATTENTION_SIZES == {"units": (32, 64), "max_edge_width": 64, "max_heads_per_launch": 8}
+    assert _ffi.MP_GAT_MAX_HEADS == 8
+    ok = gat_conv.fused_attention_supported
+    act = "kgcnn>leaky_relu"
+    assert ok(32, act) and ok(64, act) and ok(64, "relu") and ok(32, "tanh")
+    for units in (2, 5, 16, 24, 33, 128):
+        assert not ok(units, act)
+    assert ok(32, act, use_edge_features=True, edge_width=64) and ok(32, act, use_edge_features=True, edge_width=1)
+    assert not ok(32, act, use_edge_features=True, edge_width=65)
+    assert not ok(32, act, use_edge_features=True, edge_width=None)
+    assert ok(32, act, use_edge_features=False, edge_width=500)        # the edges are not read
+    assert not ok(32, "elu") and not ok(32, "softmax")
+    assert not ok(32, act, dtype="float64") and ok(32, act, dtype=torch.float32)
+    assert not ok(32, act, pooling_index=1) and not ok(32, act, has_unconnected=False)
+
+
+def test_heads_of_a_block_must_match():
+    ok = gat_conv.fused_attention_supported
+    a, b = gat_conv.AttentionHeadGAT(32), gat_conv.AttentionHeadGAT(32)
+    assert ok(32, "kgcnn>leaky_relu", heads=[a, b])
+    assert not ok(32, "kgcnn>leaky_relu", heads=[a, gat_conv.AttentionHeadGATV2(32)])
+    assert not ok(32, "kgcnn>leaky_relu", heads=[a, gat_conv.AttentionHeadGAT(32, use_bias=False)])
+    assert not ok(32, "kgcnn>leaky_relu", heads=[a, gat_conv.AttentionHeadGAT(32, activation="relu")])
+    assert not ok(32, "kgcnn>leaky_relu", heads=[a, gat_conv.AttentionHeadGAT(32, use_final_activation=False)])
+    assert not ok(32, "kgcnn>leaky_relu", heads=[])
+    block = gat_conv.FusedAttentionBlock([a, b])
+    assert block.supported(None)
+    b.use_fused_attention = False
+    assert not block.supported(None)
+    b.use_fused_attention = True
+    b.lay_pool_attention.pooling_index = 1
+    assert not block.supported(None)
+
+
+HEAD_KEYS = {"use_edge_features", "use_bias", "units", "has_self_loops", "use_final_activation", "activation",
+             "kernel_regularizer", "activity_regularizer", "bias_regularizer", "kernel_constraint", "bias_constraint",
+             "kernel_initializer", "bias_initializer"}
+
+
+def test_config_keys_unchanged():
+    base = set(gat_conv.GraphBaseLayer().get_config())
+    for lay in (gat_conv.AttentionHeadGAT(32), gat_conv.AttentionHeadGATV2(32)):
+        assert set(lay.get_config()) == base | HEAD_KEYS
+        assert lay.use_fused_attention is True
+    multi = gat_conv.MultiHeadGATV2Layer(units=32, num_heads=3)
+    assert set(multi.get_config()) == base | HEAD_KEYS | {"num_heads", "concat_heads"}
+    assert multi.use_fused_attention is True
+
+
+def test_model_switch_and_served_blocks():
+    from gcnn_keras_amd.literature import GAT, GATv2
+    for builder in (GAT, GATv2):
+        m = builder.make_model()
+        assert m.fused_attention_blocks == [True] * 3 and len(m.attention_heads) == 15 and m.use_fused_attention is True
+        m.use_fused_attention = False
+        assert not any(h.use_fused_attention for h in m.attention_heads) and m.use_fused_attention is False
+        m.use_fused_attention = True
+        m.attention_heads[7].use_fused_attention = False
+        assert m.use_fused_attention is False
+        small = builder.make_model(attention_args={"units": 24})
+        assert small.fused_attention_blocks == [False] * 3
+
+
+def test_new_symbols_in_header_and_table():
+    text = open(os.path.join(ROOT, "include", "mpengine.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    declared = set(re.findall(r"\b(mp_[a-z0-9_]+)\s*\(", text))
+    for name in NEW_SYMBOLS:
+        assert name in declared and name in _ffi.declared_symbols(), name
+        assert hasattr(_ffi.lib(), name), name
+
+
+def test_argument_errors_and_empty_problems():
+    lib = _ffi.lib()
+    # (mode, H, U, P, Q, pq, Wc, b, a, N, edges, D, cols, E, perm0, act, alpha, logits, logit_heads, head0, stream)
+    logits = lambda mode=1, h=1, u=32, n=4, d=0, e=0, act=0, lh=1, h0=0: lib.mp_gat_logits_f32(
+        mode, h, u, None, None, None, None, None, None, n, None, d, None, e, None, act, 0.05, None, lh, h0, None)
+    assert logits() == _ffi.MP_OK                      # no edges: nothing to launch
+    assert logits(mode=2) == _ffi.MP_EINVAL and b"mp_gat_logits_f32" in lib.mp_last_error()
+    assert logits(h=9) == _ffi.MP_EINVAL and logits(h=0) == _ffi.MP_EINVAL
+    assert logits(u=48) == _ffi.MP_EINVAL
+    assert logits(d=65) == _ffi.MP_EINVAL and logits(mode=0, d=65) == _ffi.MP_OK
+    assert logits(act=99) == _ffi.MP_EINVAL
+    assert logits(h=5, lh=4) == _ffi.MP_EINVAL and logits(h=5, lh=8, h0=4) == _ffi.MP_EINVAL
+    assert logits(e=2 ** 31) == _ffi.MP_EINVAL
+    assert logits(e=3) == _ffi.MP_EINVAL               # edges without pointers
+    scores = lambda h=1, u=32, n=0: lib.mp_gat_node_scores_f32(h, u, None, None, n, None, None)
+    assert scores() == _ffi.MP_OK and scores(h=9) == _ffi.MP_EINVAL and scores(u=8) == _ffi.MP_EINVAL
+    assert scores(n=3) == _ffi.MP_EINVAL and b"mp_gat_node_scores_f32" in lib.mp_last_error()
+    attend = lambda h=1, u=32, n=0, e=0, lh=1, h0=0: lib.mp_gat_attend_f32(h, u, None, n, None, lh, h0, None, e, None, None,
+                                                                          None, None)
+    assert attend() == _ffi.MP_OK
+    assert attend(h=9) == _ffi.MP_EINVAL and attend(u=16) == _ffi.MP_EINVAL and attend(lh=1, h0=1) == _ffi.MP_EINVAL
+    assert attend(n=3) == _ffi.MP_EINVAL and b"mp_gat_attend_f32" in lib.mp_last_error()
+    assert lib.mp_segment_softmax_csr_grad_f32(None, None, 0, 1, None, None, 0, None, None) == _ffi.MP_OK
+    assert lib.mp_segment_softmax_csr_grad_f32(None, None, 3, 1, None, None, 2, None, None) == _ffi.MP_EINVAL
+    assert lib.mp_segment_weight_grad_f32(None, None, 0, 4, None, 0, None, None) == _ffi.MP_OK
+    assert lib.mp_segment_weight_grad_f32(None, None, 3, 4, None, 2, None, None) == _ffi.MP_EINVAL
+    assert lib.mp_segment_weight_grad_f32(None, None, 3, 0, None, 2, None, None) == _ffi.MP_EINVAL
+
+
+def test_binary_crossentropy_hand_computation():
+    p = np.array([[0.9, 0.2], [0.5, 1.0], [0.0, 0.3]], np.float32)
+    y = np.array([[1.0, 0.0], [1.0, 1.0], [0.0, 1.0]], np.float32)
+    eps = 1e-7
+    pc = np.clip(p.astype(np.float64), eps, 1 - eps)
+    per = -(y * np.log(pc + eps) + (1 - y) * np.log(1 - pc + eps)).mean(axis=-1)
+    got = losses.binary_crossentropy(torch.from_numpy(p), torch.from_numpy(y))
+    np.testing.assert_allclose(float(got), per.mean(), rtol=1e-6)
+    w = np.array([2.0, 0.0, 0.5], np.float32)
+    got_w = losses.binary_crossentropy(torch.from_numpy(p), y, sample_weight=w)
+    np.testing.assert_allclose(float(got_w), (per * w).mean(), rtol=1e-6)       # weight-zero samples count in the mean
+    assert losses.get_loss("binary_crossentropy") is losses.binary_crossentropy
+    pt = torch.tensor(p[:1], requires_grad=True)
+    losses.binary_crossentropy(pt, y[:1]).backward()
+    np.testing.assert_allclose(pt.grad.numpy(), [[-0.5 / 0.9, 0.5 / 0.8]], rtol=1e-5)
+
+
+def test_unknown_loss_still_raises():
+    with pytest.raises(ValueError):
+        losses.get_loss("nope")
+
+
+# ------------------------------------------------------------------------------------------ restatement vs NumPy oracle
+def _small_batch(seed=3, fn=7, fe=4):
+    from gcnn_keras_amd import synth
+    b = synth.qm9_like_batch(num_graphs=4, seed=seed)
+    rng = np.random.default_rng(seed + 1)
+    n, m = int(b["node_splits"][-1]), int(b["edge_splits"][-1])
+    b["x"] = rng.normal(size=(n, fn)).astype(np.float32)
+    b["e"] = rng.normal(size=(m, fe)).astype(np.float32)
+    b["flat"] = b["edge_indices"] + np.repeat(b["node_splits"][:-1], np.diff(b["edge_splits"]))[:, None]
+    return b
+
+
+@pytest.mark.parametrize("v2", [False, True])
+@pytest.mark.parametrize("use_edges,final", [(False, True), (True, False)])
+def test_restated_head_equals_the_oracle(v2, use_edges, final):
+    b = _small_batch()
+    p = gref.head_params(np.random.default_rng(5), 7, 6, 4 if use_edges else 0, v2)
+    fn = ko.attention_head_gatv2 if v2 else ko.attention_head_gat
+    ref = fn(ko.R(b["x"], b["node_splits"]), ko.R(b["e"], b["edge_splits"]), ko.R(b["edge_indices"], b["edge_splits"]), p,
+             use_edge_features=use_edges, use_final_activation=final).values
+    for dt, tol in ((torch.float32, 2e-6), (torch.float64, 2e-6)):
+        out, logits = gref.head(torch.tensor(b["x"], dtype=dt), torch.tensor(b["e"], dtype=dt), b["flat"],
+                                gref.params_to(p, dt), v2, use_edge_features=use_edges, use_final_activation=final)
+        assert logits.shape == (len(b["flat"]), 1)
+        assert max_rel(out.numpy(), ref) <= tol, dt
+
+
+@pytest.mark.parametrize("v2,concat", [(False, False), (True, True)])
+def test_restated_model_equals_the_oracle(v2, concat):
+    b = _small_batch(seed=9)
+    p = gref.model_params(np.random.default_rng(11), 7, 4, 6, 3, 2, concat, v2)
+    ref = ko.gat_forward(p, ko.R(b["x"], b["node_splits"]), ko.R(b["e"], b["edge_splits"]),
+                         ko.R(b["edge_indices"], b["edge_splits"]), depth=2, heads=3, concat_heads=concat, v2=v2)
+    for dt in (torch.float32, torch.float64):
+        out = gref.model_forward(gref.params_to(p, dt), torch.tensor(b["x"], dtype=dt), torch.tensor(b["e"], dtype=dt),
+                                 b["flat"], b["node_splits"], depth=2, heads=3, concat=concat, v2=v2)
+        assert out.shape == (4, 1) and max_rel(out.numpy(), ref) <= 2e-6, dt
+
+
+def test_restated_multi_head_is_the_heads_side_by_side():
+    b = _small_batch(seed=13)
+    rng = np.random.default_rng(14)
+    heads = [gref.head_params(rng, 7, 6, 0, True) for _ in range(3)]
+    x, e = torch.tensor(b["x"], dtype=torch.float64), torch.tensor(b["e"], dtype=torch.float64)
+    ps = [gref.params_to(p, torch.float64) for p in heads]
+    h, logits = gref.multi_head(x, e, b["flat"], ps, concat=True)
+    assert h.shape == (x.shape[0], 18) and logits.shape == (len(b["flat"]), 3, 1)
+    one, lg = gref.head(x, e, b["flat"], ps[1], True, linear_activation="kgcnn>leaky_relu")
+    assert torch.equal(h[:, 6:12], one) and torch.equal(logits[:, 1], lg)
+    avg, _ = gref.multi_head(x, e, b["flat"], ps, concat=False)
+    np.testing.assert_allclose(avg.numpy(), (h[:, :6] + h[:, 6:12] + h[:, 12:]).numpy() / 3, rtol=1e-12)
+
+
+# ------------------------------------------------------------------------------------------ the GPU cases' own budget
+@pytest.mark.parametrize("v2", [False, True], ids=["gat", "gatv2"])
+@pytest.mark.parametrize("name", sorted(gref.kernel_cases()))
+def test_float32_restatement_inside_half_the_cap(name, v2):
+    case = gref.kernel_case(v2, **gref.kernel_cases()[name])
+    o32, l32 = gref.kernel_restate(case, torch.float32)
+    o64, l64 = gref.kernel_restate(case, torch.float64)
+    n, h, u = o64.shape
+    assert np.all(np.isfinite(o64)) and np.all(np.isfinite(o32))
+    assert rowwise_rel(o32.reshape(n * h, u), o64.reshape(n * h, u)) <= BAR_CAP / 2
+    if l64.size:
+        assert max_rel(l32, l64) <= 2e-6
+    if name.startswith("x40"):
+        # logits that overflow exp() in float32 unless the segment maximum is subtracted
+        assert float(np.max(np.abs(l64))) > 89.0
+
+
+def test_hub_case_has_the_shapes_it_claims():
+    import topologies as topo
+    case = gref.kernel_case(True, **gref.kernel_cases()["hub-shuffled-u64-h8-d3-f160"])
+    deg = topo.in_degrees(case["flat"], case["rows"])
+    assert deg[0] == 0 and deg[-1] == 0 and deg.max() == 1000 and 1 in deg
+    assert np.any(case["flat"][:, 0] == case["flat"][:, 1])                       # self loops
+    assert len(np.unique(case["flat"], axis=0)) < len(case["flat"])                # duplicate edges
+    assert np.any(np.diff(case["flat"][:, 0]) < 0)                                 # shuffled
+    assert np.all(np.diff(case["row_splits"]) >= 0) and 0 in np.diff(case["row_splits"])
