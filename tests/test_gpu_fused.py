@@ -300,7 +300,7 @@ def test_cfconv_deterministic_mode_on_a_real_batch_matches_default_mode():
     assert_rows_close(outs[33].cpu().numpy(), ko.schnet_cfconv(x, rbf, ridx, p).values, what="det cfconv, QM9 batch")
 
 
-def test_cfconv_no_bias_and_argument_checks():
+def test_cfconv_refuses_a_basis_wider_than_32_and_accepts_an_empty_problem():
     from gcnn_keras_amd import _ffi
     lib = _ffi.lib()
     assert lib.mp_cfconv_fused_f32(None, 4, None, 40, None, None, None, None, 3, 0, None,
