@@ -28,6 +28,7 @@ MP_PERIODIC_MAX_HITS, MP_PERIODIC_MAX_IMAGE, MP_PERIODIC_MAX_CANDIDATES = 1024, 
 MP_PERIODIC_FLAG_CAPACITY, MP_PERIODIC_FLAG_IMAGE_RANGE, MP_PERIODIC_FLAG_SINGULAR = 1, 2, 4
 MP_CMPNN_EDGE_TILE, MP_GRU_RAGGED_MAX_UNITS = 64, 512   # include/mpengine.h
 MP_GAT_V1, MP_GAT_V2, MP_GAT_MAX_HEADS = 0, 1, 8   # include/mpengine.h
+MP_RELCONV_RGCN, MP_RELCONV_FILM, MP_RELCONV_MAX_RELATIONS = 0, 1, 64   # include/mpengine.h
 
 ACTIVATION_CODES = {
     None: 0, "linear": 0, "relu": 1, "kgcnn>shifted_softplus": 2, "shifted_softplus": 2, "softplus": 3,
@@ -214,6 +215,9 @@ _SIGNATURES = {
     "mp_cmpnn_boost_f32": [P, P, c_int64, c_int64, P, P, c_int64, c_int, c_int, P, P],
     "mp_directed_edge_update_f32": [P, c_int64, P, P, c_int64, c_int64, P, P, P, P, c_int, c_int, c_float, P, P, P],
     "mp_gru_ragged_last_f32": [P, c_int64, P, c_int64, P, P, c_int64, c_int, c_int, P, P],
+    # one RGCN block (kgcnn/literature/RGCN.py:96-103) or one GNNFilm block (kgcnn/literature/GNNFilm.py:93-102)
+    "mp_relational_conv_f32": [c_int, P, c_int64, c_int64, P, c_int64, P, P, P, P, c_int64, P, P, c_int64, P, P, c_int,
+                               P, P, P, P, c_int, c_int, c_float, P, P],
     "mp_scaler_species_count": [P, c_int, P, c_int64, c_int64, P, P, P, P, P],
     "mp_scaler_fit_ws_bytes": [c_int64, c_int, P],
     "mp_scaler_normal_f64": [P, P, c_int64, P, c_int, c_int, P, c_double, c_int, P, P, P, P, c_size_t, P],

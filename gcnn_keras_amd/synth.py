@@ -728,3 +728,42 @@ def cmpnn_params(model, seed=41, dense_scale=0.5):
             v = dense_scale * glorot_uniform(rng, shape[0], shape[-1], shape=shape)
         p["%03d/%s" % (i, name)] = np.asarray(v, dtype=np.float32)
     return p
+
+
+def relational_batch(num_graphs=128, seed=7890, num_relations=20, **kwargs):
+    """``cmpnn_batch`` graphs for RGCN / GNNFilm: additionally ``edge_relations`` ``(M,)`` int64, uniform in
+    ``[0, num_relations)`` and equal for both directions of a bond, and ``edge_weights`` ``(M, 1)`` float32 in
+    ``[0.25, 1.25)``."""
+    b = cmpnn_batch(num_graphs, seed=seed, **kwargs)
+    rng = np.random.default_rng(seed + 1)
+    m = len(b["edge_indices"])
+    relations = np.zeros(m, dtype=np.int64)
+    es = b["edge_splits"]
+    for g in range(num_graphs):
+        lo, hi = int(es[g]), int(es[g + 1])
+        idx, rev = b["edge_indices"][lo:hi], b["edge_indices_reverse"][lo:hi, 0]
+        draw = rng.integers(0, num_relations, size=hi - lo)
+        forward = idx[:, 0] < idx[:, 1]
+        relations[lo:hi] = np.where(forward, draw, draw[rev])
+    b["edge_relations"] = relations
+    b["edge_weights"] = rng.uniform(0.25, 1.25, size=(m, 1)).astype(np.float32)
+    return b
+
+
+def relational_params(model, seed=43, dense_scale=1.0):
+    """Random weights for a built RGCN / GNNFilm ``model`` in ``model.weights`` order: every kernel Glorot-uniform on its
+    last two axes times ``dense_scale`` (a relation's, a basis' or a block's own fan), ``lin_bases`` Glorot-uniform, biases
+    in +-0.1, embeddings in +-0.5."""
+    rng = np.random.default_rng(seed)
+    p = {}
+    for i, (name, t) in enumerate(model.weights):
+        shape = tuple(int(s) for s in t.shape)
+        leaf = name.rsplit("/", 1)[-1]
+        if leaf == "embeddings":
+            v = rng.uniform(-0.5, 0.5, size=shape)
+        elif leaf == "bias":
+            v = rng.uniform(-0.1, 0.1, size=shape)
+        else:
+            v = dense_scale * glorot_uniform(rng, shape[-2], shape[-1], shape=shape)
+        p["%03d/%s" % (i, name)] = np.asarray(v, dtype=np.float32)
+    return p
