@@ -35,6 +35,12 @@ ACTIVATION_CODES = {
     "swish": 4, "sigmoid": 5, "tanh": 6, "kgcnn>leaky_relu": 7, "leaky_relu": 7, "kgcnn>softplus2": 8, "softplus2": 8,
     "selu": 9, "kgcnn>swish": 4,
 }
+# ACTIVATION_CODES is the set the fused routes' `*_supported` decisions are taken on; LAYER_ACTIVATION_CODES is what the
+# Dense / Activation layers and their reverse rules run (``activation_code``): additionally Keras "elu", AttentiveFP's
+# context activation, which only csrc/mp_attentivefp.hip takes among the fused kernels.
+MP_ACT_ELU = 10   # include/mpengine.h
+LAYER_ACTIVATION_CODES = dict(ACTIVATION_CODES, elu=MP_ACT_ELU)
+MP_AFP_READOUT_MAX_UNITS = 256   # include/mpengine.h
 
 P = c_void_p
 # name -> argtypes (restype is int unless listed in _RESTYPES); mirrors include/mpengine.h one to one.
@@ -102,6 +108,7 @@ _SIGNATURES = {
     "mp_cfconv_gauss_diag_f32": [P, c_int64, P, c_int, c_float, c_float, c_float, P, P, P, P, c_int64, P, P, P],
     "mp_lstm_zero_state_f32": [P, c_int64, c_int64, c_int, c_int, P, P],
     "mp_gru_combine_f32": [P, P, P, c_int64, c_int64, c_int, c_int, P, P],
+    "mp_gru_combine_grad_f32": [P, P, P, P, c_int64, c_int64, c_int, c_int, P, P, P, P],
     "mp_batched_matvec_f32": [P, P, c_int64, c_int64, c_int64, P, P],
     "mp_painn_stage0_f32": [P, c_int, c_int64, P, c_int, c_float, P, P, P, c_int64, P, P, c_int64, P, P, c_int, c_float, c_int,
                             c_float, P, P, P, P, P, P, P, P, P, P],
@@ -218,6 +225,11 @@ _SIGNATURES = {
     # one RGCN block (kgcnn/literature/RGCN.py:96-103) or one GNNFilm block (kgcnn/literature/GNNFilm.py:93-102)
     "mp_relational_conv_f32": [c_int, P, c_int64, c_int64, P, c_int64, P, P, P, P, c_int64, P, P, c_int64, P, P, c_int,
                                P, P, P, P, c_int, c_int, c_float, P, P],
+    # AttentiveFP (csrc/mp_attentivefp.hip): the edge-feature head in two launches, the attentive readout in one
+    "mp_afp_edge_f32": [c_int, P, P, c_int64, P, c_int, P, P, P, P, P, P, P, P, c_int64, P, c_int, c_float, P, P, P],
+    "mp_afp_attend_f32": [c_int, P, P, c_int64, P, c_int64, P, P, c_int, c_float, P, P],
+    "mp_afp_readout_f32": [P, P, c_int64, P, c_int64, c_int, c_int, c_int, P, P, P, P, P, P, c_int, c_float, c_int, c_int,
+                           c_int, P, P, P],
     "mp_scaler_species_count": [P, c_int, P, c_int64, c_int64, P, P, P, P, P],
     "mp_scaler_fit_ws_bytes": [c_int64, c_int, P],
     "mp_scaler_normal_f64": [P, P, c_int64, P, c_int, c_int, P, c_double, c_int, P, P, P, P, c_size_t, P],
@@ -462,9 +474,9 @@ if os.environ.get("MPENGINE_ROCTX") == "1":
 def activation_code(name):
     if isinstance(name, dict):
         name = name.get("class_name", name.get("name"))
-    if name not in ACTIVATION_CODES:
+    if name not in LAYER_ACTIVATION_CODES:
         raise ValueError("Activation %r is not supported by the engine" % (name,))
-    return ACTIVATION_CODES[name]
+    return LAYER_ACTIVATION_CODES[name]
 
 
 def int64_array(values):

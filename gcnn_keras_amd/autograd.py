@@ -1181,3 +1181,34 @@ class EgnnEdge(torch.autograd.Function):
         _first_order_only("the fused EGNN edge step", "EGNN")
         a_bar, b_bar, x_bar = ctx.spec.grad(ctx.x, ctx.z1, ctx.z2, g, *ctx.needs_input_grad[:3])
         return a_bar, b_bar, x_bar, None
+
+
+# ---------------------------------------------------------------------------------------------------------------- GRU
+class GRUCombine(torch.autograd.Function):
+    """The GRUCell combine ``mp_gru_combine_f32`` of ``mx`` (R, 3U), ``mh`` (R, 3U) and the state ``h`` (R, U); backward
+    ``mp_gru_combine_grad_f32``, which recomputes the gates from the three inputs.  The two products that form ``mx`` and
+    ``mh`` are ``Dense`` rules of their own, so the cell's three weight gradients come from there.  First order."""
+
+    @staticmethod
+    def forward(ctx, mx, mh, h, act, rec_act):
+        mx, mh, h = mx.contiguous(), mh.contiguous(), h.contiguous()
+        ctx.act, ctx.rec_act = act, rec_act
+        ctx.save_for_backward(mx, mh, h)
+        out = torch.empty_like(h)
+        _ffi.call("mp_gru_combine_f32", _ffi.ptr(mx), _ffi.ptr(mh), _ffi.ptr(h), int(h.shape[0]), int(h.shape[1]), act,
+                  rec_act, _ffi.ptr(out), _ffi.stream())
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        mx, mh, h = ctx.saved_tensors
+        want = ctx.needs_input_grad
+        d_mx = torch.empty_like(mx) if want[0] else None
+        d_mh = torch.empty_like(mh) if want[1] else None
+        d_h = torch.empty_like(h) if want[2] else None
+        if any(want[:3]):
+            _ffi.call("mp_gru_combine_grad_f32", _ffi.ptr(mx), _ffi.ptr(mh), _ffi.ptr(h), _ffi.ptr(g.contiguous()),
+                      int(h.shape[0]), int(h.shape[1]), ctx.act, ctx.rec_act, _ffi.ptr(d_mx), _ffi.ptr(d_mh),
+                      _ffi.ptr(d_h), _ffi.stream())
+        return d_mx, d_mh, d_h, None, None

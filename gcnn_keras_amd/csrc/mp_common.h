@@ -163,6 +163,7 @@ __device__ __forceinline__ float mp_apply_act(int act, float alpha, float v) {
     case MP_ACT_LEAKY_RELU: return v >= 0.0f ? v : alpha * v;
     case MP_ACT_SOFTPLUS2: return fmaxf(v, 0.0f) + logf(0.5f * expf(-fabsf(v)) + 0.5f);
     case MP_ACT_SELU: return 1.05070098f * (v > 0.0f ? v : 1.67326324f * (expf(v) - 1.0f));
+    case MP_ACT_ELU: return v > 0.0f ? v : expm1f(v);
     default: return v;
   }
 }
@@ -180,6 +181,7 @@ __device__ __forceinline__ float mp_act_grad(int act, float alpha, float x) {
     case MP_ACT_TANH: { const float t = tanhf(x); return 1.0f - t * t; }
     case MP_ACT_LEAKY_RELU: return x >= 0.0f ? 1.0f : alpha;
     case MP_ACT_SELU: return 1.05070098f * (x > 0.0f ? 1.0f : 1.67326324f * expf(x));
+    case MP_ACT_ELU: return x > 0.0f ? 1.0f : expf(x);
     default: return 1.0f;
   }
 }
@@ -199,6 +201,7 @@ __device__ __forceinline__ float mp_act_grad2(int act, float alpha, float x) {
     case MP_ACT_SIGMOID: { const float s = mp_sigmoid(x), sm = mp_sigmoid(-x); return s * sm * (sm - s); }
     case MP_ACT_TANH: { const float t = tanhf(x); return -2.0f * t * (1.0f - t * t); }
     case MP_ACT_SELU: return x > 0.0f ? 0.0f : 1.05070098f * 1.67326324f * expf(x);
+    case MP_ACT_ELU: return x > 0.0f ? 0.0f : expf(x);
     default: return 0.0f;  // relu, leaky relu, linear
   }
 }

@@ -46,6 +46,41 @@ __global__ void gru_combine_kernel(const float* __restrict__ mx, const float* __
   }
 }
 
+// Reverse of gru_combine_kernel for an upstream gradient g (R, U).  The gates are recomputed from mx, mh and h in the
+// forward's order (nothing but its three inputs is kept on the tape).  With a_z = mx_z + mh_z, a_r = mx_r + mh_r,
+// a_h = mx_h + rg * mh_h:  d_h = g zg;  d a_z = g (h - hh) rec'(a_z);  d a_h = g (1 - zg) act'(a_h);
+// d a_r = d a_h mh_h rec'(a_r);  d_mx = [d a_z | d a_r | d a_h],  d_mh = [d a_z | d a_r | d a_h rg].
+__global__ void gru_combine_grad_kernel(const float* __restrict__ mx, const float* __restrict__ mh,
+                                        const float* __restrict__ h, const float* __restrict__ g, int64_t R, int64_t U,
+                                        int act, int rec_act, float* __restrict__ d_mx, float* __restrict__ d_mh,
+                                        float* __restrict__ d_h) {
+  const int64_t total = R * U;
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
+  for (int64_t t = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; t < total; t += stride) {
+    const int64_t r = t / U, u = t % U;
+    const float* x = mx + r * 3 * U;
+    const float* y = mh + r * 3 * U;
+    const float az = x[u] + y[u], ar = x[U + u] + y[U + u], yh = y[2 * U + u];
+    const float zg = mp_apply_act(rec_act, 0.0f, az);
+    const float rg = mp_apply_act(rec_act, 0.0f, ar);
+    const float ah = x[2 * U + u] + rg * yh;
+    const float hh = mp_apply_act(act, 0.0f, ah);
+    const float gt = g[t];
+    const float daz = gt * (h[t] - hh) * mp_act_grad(rec_act, 0.0f, az);
+    const float dah = gt * (1.0f - zg) * mp_act_grad(act, 0.0f, ah);
+    const float dar = dah * yh * mp_act_grad(rec_act, 0.0f, ar);
+    if (d_h) d_h[t] = gt * zg;
+    if (d_mx) {
+      float* o = d_mx + r * 3 * U;
+      o[u] = daz; o[U + u] = dar; o[2 * U + u] = dah;
+    }
+    if (d_mh) {
+      float* o = d_mh + r * 3 * U;
+      o[u] = daz; o[U + u] = dar; o[2 * U + u] = dah * rg;
+    }
+  }
+}
+
 // out[m][r] = sum_c mat[m][r][c] vec[m][c].  LPR = C / 4 lanes share a row (one float4 each), so a wave instruction reads
 // 64 / LPR whole rows = 1 KB contiguous; the LPR partial dot products are reduced with log2(LPR) xor shuffles.
 template <int LPR>
@@ -295,6 +330,20 @@ int mp_gru_combine_f32(const float* mx, const float* mh, const float* h, int64_t
   MP_REQUIRE(mx && mh && h && out, "mp_gru_combine_f32: null pointer");
   gru_combine_kernel<<<mp::grid_for(R * U), 256, 0, mp::as_stream(stream)>>>(mx, mh, h, R, U, act, rec_act, out);
   return mp::check_launch("mp_gru_combine_f32");
+}
+
+int mp_gru_combine_grad_f32(const float* mx, const float* mh, const float* h, const float* g, int64_t R, int64_t U,
+                            int act, int rec_act, float* d_mx, float* d_mh, float* d_h, mpStream_t stream) {
+  const char* what = "mp_gru_combine_grad_f32";
+  MP_REQUIRE(R >= 0 && U >= 1, "%s: bad sizes", what);
+  MP_REQUIRE(act >= MP_ACT_LINEAR && act <= MP_ACT_LAST && rec_act >= MP_ACT_LINEAR && rec_act <= MP_ACT_LAST,
+             "%s: unknown activation", what);
+  if (R == 0) return MP_OK;
+  MP_REQUIRE(mx && mh && h && g, "%s: null pointer", what);
+  MP_REQUIRE(d_mx || d_mh || d_h, "%s: no gradient asked for", what);
+  gru_combine_grad_kernel<<<mp::grid_for(R * U), 256, 0, mp::as_stream(stream)>>>(mx, mh, h, g, R, U, act, rec_act, d_mx,
+                                                                                 d_mh, d_h);
+  return mp::check_launch(what);
 }
 
 int mp_batched_matvec_f32(const float* mat, const float* vec, int64_t M, int64_t Ro, int64_t C, float* out,

@@ -87,7 +87,8 @@ class FusedAttentionBlock:
         self.heads = [heads] if isinstance(heads, MultiHeadGATV2Layer) else list(heads)
         self.proto = self.heads[0]
         self.triples = [tri for h in self.heads for tri in h._dense_triples()]
-        self.v2 = isinstance(self.proto, AttentionHeadGATV2)
+        # the V2 form has a hidden logit Dense (AttentionHeadGATV2 and its subclass; AttentiveHeadFP without edge features)
+        self.v2 = self.triples[0][1] is not None
 
     def supported(self, edge_width):
         """The configuration fits the kernels and every head's switch is on."""

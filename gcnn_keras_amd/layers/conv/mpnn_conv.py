@@ -64,9 +64,35 @@ class MatMulMessages(GraphBaseLayer):
         return inputs[1].with_values(out)
 
 
+def gru_cell_values(x, h, kernel, recurrent_kernel, bias, act, rec_act):
+    """One Keras GRUCell step (``reset_after=True``) on values: inputs ``x`` (R, in), state ``h`` (R, u) -> new state.
+    Without a tape two GEMMs and ``mp_gru_combine_f32``; when an operand needs grad the same three steps are recorded as
+    ``autograd.Dense`` twice and ``autograd.GRUCombine``."""
+    from ...autograd import Dense as DenseFn, GRUCombine, needs_grad
+    h, x = h.contiguous(), x.contiguous()
+    _ffi.require_device(h, x)
+    if needs_grad(x, h, kernel, recurrent_kernel, bias):
+        b_in = bias[0] if bias is not None else None
+        b_rec = bias[1] if bias is not None else None
+        mx = DenseFn.apply(x, kernel, b_in, 0, 0.0)
+        mh = DenseFn.apply(h, recurrent_kernel, b_rec, 0, 0.0)
+        return GRUCombine.apply(mx, mh, h, act, rec_act)
+    b_in = bias[0].contiguous() if bias is not None else None
+    b_rec = bias[1].contiguous() if bias is not None else None
+    mx = _dense_raw(x, kernel, b_in, 0, 0.0)
+    mh = _dense_raw(h, recurrent_kernel, b_rec, 0, 0.0)
+    out = torch.empty_like(h)
+    _ffi.call("mp_gru_combine_f32", _ffi.ptr(mx), _ffi.ptr(mh), _ffi.ptr(h), int(h.shape[0]), int(h.shape[1]), act,
+              rec_act, _ffi.ptr(out), _ffi.stream())
+    return out
+
+
 class GRUUpdate(GraphBaseLayer):
     """``GRUCell(units)(updates, state=nodes)`` on the flat values (mpnn_conv.py:111-210), Keras weight layout:
     kernel ``(in, 3u)``, recurrent_kernel ``(u, 3u)``, bias ``(2, 3u)`` (input / recurrent row), gates ``[z | r | h]``."""
+
+    # the two products are autograd.Dense, the combine autograd.GRUCombine (csrc/mp_recurrent.hip)
+    weight_gradients = True
 
     def __init__(self, units, activation="tanh", recurrent_activation="sigmoid", use_bias=True,
                  kernel_initializer="glorot_uniform", recurrent_initializer="orthogonal", bias_initializer="zeros",
@@ -100,15 +126,8 @@ class GRUUpdate(GraphBaseLayer):
 
     def call(self, inputs, **kwargs):
         inputs = self.assert_ragged_input_rank(inputs)
-        h, x = inputs[0].values.contiguous(), inputs[1].values.contiguous()
-        _ffi.require_device(h, x)
-        b_in = self.bias[0].contiguous() if self.bias is not None else None
-        b_rec = self.bias[1].contiguous() if self.bias is not None else None
-        mx = _dense_raw(x, self.kernel, b_in, 0, 0.0)
-        mh = _dense_raw(h, self.recurrent_kernel, b_rec, 0, 0.0)
-        out = torch.empty_like(h)
-        _ffi.call("mp_gru_combine_f32", _ffi.ptr(mx), _ffi.ptr(mh), _ffi.ptr(h), int(h.shape[0]), self.units, self._act,
-                  self._rec, _ffi.ptr(out), _ffi.stream())
+        out = gru_cell_values(inputs[1].values, inputs[0].values, self.kernel, self.recurrent_kernel, self.bias,
+                              self._act, self._rec)
         return inputs[0].with_values(out)
 
     def get_config(self):

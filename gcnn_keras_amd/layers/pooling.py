@@ -190,13 +190,25 @@ class PoolingLocalEdgesAttention(GraphBaseLayer):
 
 
 class PoolingEmbeddingAttention(GraphBaseLayer):
-    r"""Per-graph attention pooling ``s = sum_i softmax_i(a_i) n_i`` (kgcnn/layers/pooling.py:550-599)."""
+    r"""Per-graph attention pooling ``s = sum_i softmax_i(a_i) n_i`` (kgcnn/layers/pooling.py:550-599).  Under grad the
+    graphs are the segments of ``segment_reduce_csr`` (``autograd.SegmentSoftmax`` / ``WeightedSegmentSum``: gradients of
+    the nodes and of the attention logits); without a tape the calls are the plain kernels."""
+
+    weight_gradients = True   # layers/base.py: no weight of this layer is left off the tape
 
     def call(self, inputs, **kwargs):
         nodes, attention = self.assert_ragged_input_rank(list(inputs))
         g = nodes.nrows()
         ptr = nodes.row_splits.to(torch.int32).contiguous()
         ats = segment_softmax_csr(attention.values, ptr, None, g)
+        from ..autograd import needs_grad
+        if needs_grad(nodes.values, ats):
+            seg = nodes.value_rowids().to(torch.int32)             # graph id per node
+            splits = nodes.row_splits_host()
+            rows = g
+            while rows > 0 and splits[rows] == splits[rows - 1]:   # _pool_graph's row count: trailing empty graphs go
+                rows -= 1
+            return segment_reduce_csr(_ffi.MP_SUM, nodes.values, ptr, None, rows, weight=ats, seg_ids=seg)
         return _pool_graph(nodes, _ffi.MP_SUM, weights=nodes.with_values(ats))
 
 

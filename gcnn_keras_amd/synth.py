@@ -730,6 +730,13 @@ def cmpnn_params(model, seed=41, dense_scale=0.5):
     return p
 
 
+def attentivefp_params(model, seed=47, dense_scale=1.0):
+    """Random weights for a built AttentiveFP ``model`` in ``model.weights`` order (``cmpnn_params``' rules: Dense kernels
+    Glorot-uniform times ``dense_scale``, the GRU cells' kernels full Glorot-uniform, biases in +-0.1, embeddings in
+    +-0.5).  ``cmpnn_batch`` gives the bond graphs, with integer types for the embedding inputs and float features."""
+    return cmpnn_params(model, seed=seed, dense_scale=dense_scale)
+
+
 def relational_batch(num_graphs=128, seed=7890, num_relations=20, **kwargs):
     """``cmpnn_batch`` graphs for RGCN / GNNFilm: additionally ``edge_relations`` ``(M,)`` int64, uniform in
     ``[0, num_relations)`` and equal for both directions of a bond, and ``edge_weights`` ``(M, 1)`` float32 in

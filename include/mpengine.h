@@ -43,7 +43,8 @@ enum mp_activation {
   MP_ACT_SIGMOID = 5, MP_ACT_TANH = 6, MP_ACT_LEAKY_RELU = 7,
   MP_ACT_SOFTPLUS2 = 8, /* kgcnn/ops/activ.py:19-29: relu(x) + log(0.5 exp(-|x|) + 0.5) */
   MP_ACT_SELU = 9,      /* Keras "selu" (kgcnn/literature/NMPN.py:41): scale * (x > 0 ? x : alpha * (exp(x) - 1)) */
-  MP_ACT_LAST = MP_ACT_SELU
+  MP_ACT_ELU = 10,      /* Keras "elu", alpha = 1 (kgcnn/layers/conv/attentivefp_conv.py:38): x > 0 ? x : exp(x) - 1 */
+  MP_ACT_LAST = MP_ACT_ELU
 };
 
 enum mp_binary_op { MP_ADD = 0, MP_SUB = 1, MP_MUL = 2 };
@@ -322,6 +323,11 @@ int mp_lstm_zero_state_f32(const float* z, int64_t R, int64_t U, int act, int re
  * zg = rec(mx_z + mh_z), rg = rec(mx_r + mh_r), hh = act(mx_h + rg * mh_h), out = zg * h + (1 - zg) * hh. */
 int mp_gru_combine_f32(const float* mx, const float* mh, const float* h, int64_t R, int64_t U, int act, int rec_act,
                        float* out, mpStream_t stream);
+/* Reverse of mp_gru_combine_f32 for the upstream gradient g (R,U): d_mx (R,3U), d_mh (R,3U) and d_h (R,U), each
+ * nullable (at least one given).  The gates are recomputed from mx, mh and h in the forward's order; elementwise, no
+ * reduction: equal bits on every run. */
+int mp_gru_combine_grad_f32(const float* mx, const float* mh, const float* h, const float* g, int64_t R, int64_t U,
+                            int act, int rec_act, float* d_mx, float* d_mh, float* d_h, mpStream_t stream);
 /* MatMulMessages, kgcnn/layers/conv/mpnn_conv.py:111 (tf.keras.backend.batch_dot): out[m] = mat[m] (Ro,C) . vec[m] (C). */
 int mp_batched_matvec_f32(const float* mat, const float* vec, int64_t M, int64_t Ro, int64_t C, float* out,
                           mpStream_t stream);
@@ -1143,6 +1149,40 @@ int mp_relational_conv_f32(int mode, const float* nodes, int64_t N, int64_t K, c
                            int64_t R, const float* W, const float* b, int64_t U, const float* W0, const float* b0,
                            int act0, const float* Wg, const float* bg, const float* Wt, const float* bt, int act_m,
                            int act, float alpha, float* out, mpStream_t stream);
+
+/* ---------------------------------------------------------------- AttentiveFP: edge head, attentive readout --------- */
+/* csrc/mp_attentivefp.hip, which states the algebra (kgcnn/layers/conv/attentivefp_conv.py:75-107, 196-220).
+ *
+ * mp_afp_edge_f32: the per-edge part of AttentiveHeadFP with use_edge_features, over receiver-sorted positions p
+ *   (edge e = perm0[p], r = cols[0][e], s = cols[1][e], g_e = edges[e] (E, D)):
+ *     hidden = act(X[s] + g_e W2e + b2),  msg[p] = hidden Wl + bl,  logit[p] = a . act(P[r] + hidden Wae + ba)
+ *   X, P (N, U) node-side products; W2e (D, U), Wl, Wae (U, U) row-block views of the layers' kernels, read in place;
+ *   every bias (U) nullable; a (U).  logit (E) and msg (E, U) are written in POSITION order; a position whose edge id,
+ *   receiver or sender is out of range gets zeros.  U in {32, 64}, 1 <= D <= 64 (MP_EINVAL otherwise).  E = 0 needs no
+ *   device.
+ * mp_afp_attend_f32: out[r] = act_context(sum_p softmax_p(logit[p]) msg[p]) over the positions [ptr0[r], ptr0[r + 1]),
+ *   the segment maximum subtracted before the exponential; out (N, U), every row written, a receiver without edges gets
+ *   act_context(0).  One wave per receiver, the sweeps of mp_gat_attend_f32.  N = 0 needs no device.
+ * mp_afp_readout_f32: PoolingNodesAttentive.call behind its Dense (wn = n Wl + bl), the loop over `depth` inside one
+ *   launch: h_g = pool_op (MP_SUM / MP_MEAN) of the graph's rows of n (n_nodes, U); per iteration
+ *   a_i = act(w . [h_g || n_i] + b), cont_g = act_context(sum_i softmax_i(a_i) wn_i), h_g = GRUCell(cont_g, h_g) with
+ *   K, R (U, 3U), b_in, b_rec (3U) nullable, gates [z | r | h], the combine of mp_gru_combine_f32.  w (2U), b (1)
+ *   nullable; node_term: workspace of n_nodes doubles; out (G, U); a graph without nodes runs the recurrence on
+ *   cont = act_context(0).  U a multiple of 4, at most MP_AFP_READOUT_MAX_UNITS; depth >= 0.  A workgroup carries 16
+ *   graphs.  G = 0 needs no device.
+ * All three: no float atomics, equal bits on every run and stream, no host read-back; forward only. */
+#define MP_AFP_READOUT_MAX_UNITS 256
+int mp_afp_edge_f32(int U, const float* X, const float* P, int64_t N, const float* edges, int D, const float* W2e,
+                    const float* b2, const float* Wl, const float* bl, const float* Wae, const float* ba, const float* a,
+                    const int32_t* cols, int64_t E, const int32_t* perm0, int act, float alpha, float* logit, float* msg,
+                    mpStream_t stream);
+int mp_afp_attend_f32(int U, const float* msg, const float* logit, int64_t N, const int32_t* cols, int64_t E,
+                      const int32_t* ptr0, const int32_t* perm0, int act_context, float alpha, float* out,
+                      mpStream_t stream);
+int mp_afp_readout_f32(const float* n, const float* wn, int64_t n_nodes, const int64_t* row_splits, int64_t G, int U,
+                       int depth, int pool_op, const float* w, const float* b, const float* K, const float* R,
+                       const float* b_in, const float* b_rec, int act, float alpha, int act_context, int gru_act,
+                       int rec_act, double* node_term, float* out, mpStream_t stream);
 
 /* ---------------------------------------------------------------- extensive energy / force label scaler ------------
  * kgcnn/data/transform/scaler/mol.py:38-98 (_ExtensiveMolecularScalerBase._fit / _predict) and

@@ -1,0 +1,387 @@
+"""AttentiveFP on the engine: the restatement the GPU tests measure against (pinned to a per-edge / per-graph NumPy
+loop), the row-block identities the kernels rest on, configs, weight names and order, refusals, the configuration rules,
+the new ABI symbols and the GPU cases' own float32 budget.  Runs without a GPU."""
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import attentivefp_reference as aref
+from gcnn_keras_amd import _ffi
+from gcnn_keras_amd.layers.base import GraphBaseLayer
+from gcnn_keras_amd.layers.conv import attentivefp_conv as afp
+from gcnn_keras_amd.literature import AttentiveFP
+from parity import BAR_CAP, max_rel, rowwise_rel
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW_SYMBOLS = ("mp_afp_edge_f32", "mp_afp_attend_f32", "mp_afp_readout_f32", "mp_gru_combine_grad_f32")
+F64 = torch.float64
+
+
+# ------------------------------------------------------------------------------------------ restatement vs NumPy loops
+def _np_act(name, x):
+    if name in ("kgcnn>leaky_relu", "leaky_relu"):
+        return np.where(x >= 0, x, 0.05 * x)
+    return {"elu": lambda v: np.where(v > 0, v, np.expm1(np.minimum(v, 0.0))), "tanh": np.tanh, "linear": lambda v: v,
+            "sigmoid": lambda v: 1.0 / (1.0 + np.exp(-v)), "relu": lambda v: np.maximum(v, 0.0)}[name](x)
+
+
+def _np_dense(x, p, name, act):
+    y = x @ p[name + "/kernel"].astype(np.float64)
+    if name + "/bias" in p:
+        y = y + p[name + "/bias"]
+    return _np_act(act, y)
+
+
+def _head_loop(node, edge, flat, p, use_edges, act="kgcnn>leaky_relu", ctx="elu"):
+    """One edge at a time, then one receiver at a time."""
+    node, edge = node.astype(np.float64), edge.astype(np.float64)
+    msgs, logits = [], []
+    for (r, s), g in zip(flat, edge):
+        n_in, n_out = node[r], node[s]
+        if use_edges:
+            n_in = _np_dense(n_in, p, "fc1", act)
+            n_out = _np_dense(np.concatenate([n_out, g]), p, "fc2", act)
+        msgs.append(_np_dense(n_out, p, "linear_trafo", "linear"))
+        hid = _np_dense(np.concatenate([n_in, n_out]), p, "alpha_activation", act)
+        logits.append(float(hid @ p["alpha/kernel"].astype(np.float64)[:, 0]))
+    u = p["linear_trafo/kernel"].shape[1]
+    out = np.zeros((len(node), u))
+    for r in range(len(node)):
+        mine = [k for k in range(len(flat)) if flat[k, 0] == r]
+        if mine:
+            a = np.array([logits[k] for k in mine])
+            w = np.exp(a - a.max())
+            w /= w.sum()
+            out[r] = sum(wk * msgs[k] for wk, k in zip(w, mine))
+    return _np_act(ctx, out), np.array(logits)
+
+
+def _gru_loop(x, h, p, prefix="gru"):
+    u = len(h)
+    mx, mh = x @ p[prefix + "/kernel"].astype(np.float64), h @ p[prefix + "/recurrent_kernel"].astype(np.float64)
+    if prefix + "/bias" in p:
+        mx, mh = mx + p[prefix + "/bias"][0], mh + p[prefix + "/bias"][1]
+    z = _np_act("sigmoid", mx[:u] + mh[:u])
+    r = _np_act("sigmoid", mx[u:2 * u] + mh[u:2 * u])
+    hh = np.tanh(mx[2 * u:] + r * mh[2 * u:])
+    return z * h + (1 - z) * hh
+
+
+def _readout_loop(node, splits, p, depth, pooling, act="kgcnn>leaky_relu", ctx="elu"):
+    """One graph at a time."""
+    node = node.astype(np.float64)
+    out = []
+    for g in range(aref.graph_rows(splits)):
+        rows = node[splits[g]:splits[g + 1]]
+        h = rows.sum(axis=0) if len(rows) else np.zeros(node.shape[1])
+        if pooling == "mean" and len(rows):
+            h = h / len(rows)
+        wn = _np_dense(rows, p, "linear_trafo", "linear")
+        for _ in range(depth):
+            cont = np.zeros(node.shape[1])
+            if len(rows):
+                a = np.array([_np_dense(np.concatenate([h, n_i]), p, "alpha", act)[0] for n_i in rows])
+                w = np.exp(a - a.max())
+                cont = (w / w.sum()) @ wn
+            h = _gru_loop(_np_act(ctx, cont), h, p)
+        out.append(h)
+    return np.array(out).reshape(len(out), node.shape[1])
+
+
+def _small_batch(seed=3, fn=7, fe=4, num_graphs=4):
+    from gcnn_keras_amd import synth
+    b = synth.cmpnn_batch(num_graphs=num_graphs, seed=seed, node_features=fn, edge_features=fe)
+    b["flat"] = b["edge_indices"] + np.repeat(b["node_splits"][:-1], np.diff(b["edge_splits"]))[:, None]
+    return b
+
+
+@pytest.mark.parametrize("use_edges", [False, True])
+def test_restated_head_equals_the_edge_loop(use_edges):
+    b = _small_batch()
+    p = aref.head_params(np.random.default_rng(5), 7, 6, 4 if use_edges else 0)
+    ref, ref_logits = _head_loop(b["node_attributes"], b["edge_attributes"], b["flat"], p, use_edges)
+    out, logits = aref.head(torch.tensor(b["node_attributes"], dtype=F64), torch.tensor(b["edge_attributes"], dtype=F64),
+                            b["flat"], aref.params_to(p, F64), use_edges)
+    assert logits.shape == (len(b["flat"]), 1)
+    np.testing.assert_allclose(logits.numpy()[:, 0], ref_logits, rtol=1e-12, atol=1e-13)
+    np.testing.assert_allclose(out.numpy(), ref, rtol=1e-11, atol=1e-13)
+
+
+@pytest.mark.parametrize("pooling,depth", [("sum", 3), ("mean", 1), ("sum", 0)])
+def test_restated_readout_equals_the_graph_loop(pooling, depth):
+    rng = np.random.default_rng(8)
+    splits = np.array([0, 0, 5, 6, 6, 19, 19], np.int64)           # empty first, interior and last
+    node = rng.normal(size=(19, 8)).astype(np.float32)
+    p = aref.readout_params(rng, 8)
+    out = aref.readout(torch.tensor(node, dtype=F64), splits, aref.params_to(p, F64), depth, pooling).numpy()
+    assert out.shape == (5, 8)                                       # the trailing empty graph is dropped
+    np.testing.assert_allclose(out, _readout_loop(node, splits, p, depth, pooling), rtol=1e-11, atol=1e-13)
+
+
+def test_restated_model_chains_the_layers():
+    b = _small_batch(seed=9)
+    p = aref.model_params(np.random.default_rng(11), 7, 4, 8)
+    x, e = b["node_attributes"].astype(np.float64), b["edge_attributes"].astype(np.float64)
+    nk = x @ p["dense0/kernel"] + p["dense0/bias"]
+    for i in range(2):
+        ck, _ = _head_loop(nk, e, b["flat"], aref.sub(p, "head%d/" % i), i == 0)
+        nk = np.array([_gru_loop(c, h, aref.sub(p, "update%d/" % i)) for c, h in zip(ck, nk)])
+    g = _readout_loop(nk, b["node_splits"], aref.sub(p, "readout/"), 2, "sum")
+    g = np.maximum(g @ p["output_mlp/0/kernel"] + p["output_mlp/0/bias"], 0.0)
+    g = np.maximum(g @ p["output_mlp/1/kernel"] + p["output_mlp/1/bias"], 0.0)
+    g = 1.0 / (1.0 + np.exp(-(g @ p["output_mlp/2/kernel"])))
+    out = aref.model_forward(aref.params_to(p, F64), torch.tensor(x), torch.tensor(e), b["flat"], b["node_splits"])
+    assert out.shape == (4, 1)
+    np.testing.assert_allclose(out.numpy(), g, rtol=1e-10)
+    nodes = aref.model_forward(aref.params_to(p, F64), torch.tensor(x), torch.tensor(e), b["flat"], b["node_splits"],
+                               output_embedding="node")
+    assert nodes.shape == (len(x), 1)
+
+
+# ------------------------------------------------------------------------------------------ the kernels' identities
+def test_row_block_identities():
+    """float64: fc2 on the concatenation is the sender's product plus the edge product; the hidden logit Dense splits at
+    row U; the readout's logit is a per-graph term plus a loop-invariant per-node term."""
+    rng = np.random.default_rng(21)
+    n, m, f, d, u = 9, 30, 7, 5, 6
+    node, g = torch.tensor(rng.normal(size=(n, f))), torch.tensor(rng.normal(size=(m, d)))
+    recv, send = torch.tensor(rng.integers(0, n, size=m)), torch.tensor(rng.integers(0, n, size=m))
+    p = aref.params_to(aref.head_params(rng, f, u, d), F64)
+    act = aref.ACTIVATIONS["kgcnn>leaky_relu"]
+    w2, wa = p["fc2/kernel"], p["alpha_activation/kernel"]
+    hidden = act(torch.cat([node[send], g], dim=-1) @ w2 + p["fc2/bias"])
+    x = node @ w2[:f]
+    np.testing.assert_allclose((act(x[send] + g @ w2[f:] + p["fc2/bias"])).numpy(), hidden.numpy(), rtol=1e-12, atol=1e-14)
+    a1 = act(node @ p["fc1/kernel"] + p["fc1/bias"])
+    full = act(torch.cat([a1[recv], hidden], dim=-1) @ wa + p["alpha_activation/bias"])
+    split = act((a1 @ wa[:u])[recv] + hidden @ wa[u:] + p["alpha_activation/bias"])
+    np.testing.assert_allclose(split.numpy(), full.numpy(), rtol=1e-12, atol=1e-14)
+    # the readout
+    q = aref.params_to(aref.readout_params(rng, f), F64)
+    graph = torch.tensor([0, 0, 0, 1, 1, 2, 2, 2, 2])
+    h = torch.tensor(rng.normal(size=(3, f)))
+    w = q["alpha/kernel"][:, 0]
+    full = torch.cat([h[graph], node], dim=-1) @ q["alpha/kernel"] + q["alpha/bias"]
+    split = (h @ w[:f] + q["alpha/bias"])[graph] + node @ w[f:]
+    np.testing.assert_allclose(split.numpy(), full.numpy()[:, 0], rtol=1e-12, atol=1e-14)
+
+
+def test_gru_combine_reverse_formulas():
+    """The closed forms csrc/mp_recurrent.hip's reverse kernel evaluates, against float64 autograd."""
+    rng = np.random.default_rng(23)
+    r, u = 5, 4
+    mx, mh, h = (torch.tensor(rng.normal(size=s), requires_grad=True) for s in ((r, 3 * u), (r, 3 * u), (r, u)))
+    g = torch.tensor(rng.normal(size=(r, u)))
+    az, ar = mx[:, :u] + mh[:, :u], mx[:, u:2 * u] + mh[:, u:2 * u]
+    zg, rg = torch.sigmoid(az), torch.sigmoid(ar)
+    ah = mx[:, 2 * u:] + rg * mh[:, 2 * u:]
+    hh = torch.tanh(ah)
+    out = zg * h + (1 - zg) * hh
+    d_mx, d_mh, d_h = torch.autograd.grad(out, [mx, mh, h], g)
+    with torch.no_grad():
+        daz = g * (h - hh) * zg * (1 - zg)
+        dah = g * (1 - zg) * (1 - hh * hh)
+        dar = dah * mh[:, 2 * u:] * rg * (1 - rg)
+        np.testing.assert_allclose(torch.cat([daz, dar, dah], dim=1).numpy(), d_mx.numpy(), rtol=1e-12, atol=1e-15)
+        np.testing.assert_allclose(torch.cat([daz, dar, dah * rg], dim=1).numpy(), d_mh.numpy(), rtol=1e-12, atol=1e-15)
+        np.testing.assert_allclose((g * zg).numpy(), d_h.numpy(), rtol=1e-12, atol=1e-15)
+
+
+# ------------------------------------------------------------------------------------------ configs, weights, refusals
+KERNEL_KEYS = {"kernel_regularizer", "activity_regularizer", "bias_regularizer", "kernel_constraint", "bias_constraint",
+               "kernel_initializer", "bias_initializer"}
+HEAD_KEYS = KERNEL_KEYS | {"use_edge_features", "use_bias", "units", "activation", "activation_context"}
+READOUT_KEYS = KERNEL_KEYS | {"units", "depth", "pooling_method", "activation", "use_bias", "activation_context",
+                              "recurrent_activation", "recurrent_initializer", "recurrent_regularizer",
+                              "recurrent_constraint", "dropout", "recurrent_dropout", "reset_after"}
+
+
+def test_config_round_trips():
+    base = set(GraphBaseLayer().get_config())
+    head = afp.AttentiveHeadFP(32, use_edge_features=True, activation="relu", activation_context="tanh", use_bias=False)
+    conf = head.get_config()
+    assert set(conf) == base | HEAD_KEYS
+    assert (conf["units"], conf["activation"], conf["activation_context"], conf["use_bias"]) == (32, "relu", "tanh", False)
+    assert afp.AttentiveHeadFP.from_config(conf).get_config() == conf
+    assert afp.AttentiveHeadFP(32).get_config()["activation_context"] == "elu" and head.use_fused_attentive is True
+    pool = afp.PoolingNodesAttentive(36, depth=2, pooling_method="mean")
+    conf = pool.get_config()
+    assert set(conf) == base | READOUT_KEYS
+    assert (conf["units"], conf["depth"], conf["pooling_method"], conf["reset_after"]) == (36, 2, "mean", True)
+    assert afp.PoolingNodesAttentive.from_config(conf).get_config() == conf and pool.use_fused_attentive is True
+
+
+def test_weight_names_and_order():
+    head = afp.AttentiveHeadFP(32, use_edge_features=True)
+    head.ensure_built([(None, None, 20), (None, None, 6), (None, None, 2)])
+    owners = [name.split("/")[0] for name, _ in head.weights]
+    subs = {lay.name: attr for attr, lay in vars(head).items() if attr.startswith("lay_")}
+    assert [subs[o] for o in owners] == ["lay_linear_trafo"] * 2 + ["lay_alpha_activation"] * 2 + ["lay_alpha"] + \
+        ["lay_fc1"] * 2 + ["lay_fc2"] * 2
+    assert [tuple(t.shape) for _, t in head.weights] == [(32, 32), (32,), (64, 32), (32,), (32, 1), (20, 32), (32,), (26, 32), (32,)]
+    plain = afp.AttentiveHeadFP(32)
+    plain.ensure_built([(None, None, 20), (None, None, 6), (None, None, 2)])
+    assert [tuple(t.shape) for _, t in plain.weights] == [(20, 32), (32,), (40, 32), (32,), (32, 1)]
+    pool = afp.PoolingNodesAttentive(36)
+    pool.ensure_built((None, None, 36))
+    assert [name for name, _ in pool.weights][-3:] == ["gru_cell/kernel", "gru_cell/recurrent_kernel", "gru_cell/bias"]
+    assert [tuple(t.shape) for _, t in pool.weights] == [(36, 36), (36,), (72, 1), (1,), (36, 108), (36, 108), (2, 108)]
+    # the restatement's parameter dictionaries follow the same order
+    assert [tuple(v.shape) for v in aref.head_params(np.random.default_rng(0), 20, 32, 6).values()] == \
+        [tuple(t.shape) for _, t in head.weights]
+    assert [tuple(v.shape) for v in aref.readout_params(np.random.default_rng(0), 36).values()] == \
+        [tuple(t.shape) for _, t in pool.weights]
+    model = AttentiveFP.make_model()
+    p = aref.model_params(np.random.default_rng(0), 64, 64, 32, embed=(95, 5))
+    assert [tuple(v.shape) for v in p.values()] == [tuple(t.shape) for _, t in model.weights]
+
+
+def test_refusals():
+    for kwargs in ({"reset_after": False}, {"dropout": 0.1}, {"recurrent_dropout": 0.2}):
+        with pytest.raises(NotImplementedError):
+            afp.PoolingNodesAttentive(32, **kwargs)
+    with pytest.raises(ValueError, match="node width"):
+        afp.PoolingNodesAttentive(32).ensure_built((None, None, 20))
+    with pytest.raises(ValueError, match="Unsupported graph embedding"):
+        AttentiveFP.make_model(output_embedding="edge")
+    with pytest.raises(ValueError):
+        AttentiveFP.make_model(no_such_key=1)
+
+
+def test_gru_update_and_attention_pooling_are_on_the_tape_now():
+    from gcnn_keras_amd.layers.conv.mpnn_conv import GRUUpdate
+    from gcnn_keras_amd.layers.pooling import PoolingNodesAttention
+    assert GRUUpdate.weight_gradients is True and PoolingNodesAttention.weight_gradients is True
+    assert afp.AttentiveHeadFP.weight_gradients is True and afp.PoolingNodesAttentive.weight_gradients is True
+    from gcnn_keras_amd import autograd
+    assert hasattr(autograd, "GRUCombine")
+
+
+def test_served_sizes():
+    assert afp.FUSED_ATTENTIVE_SIZES == {"head_units": (32, 64), "max_edge_width": 64, "max_readout_units": 256}
+    assert _ffi.MP_AFP_READOUT_MAX_UNITS == 256
+    ok, act = afp.fused_attentive_head_supported, "kgcnn>leaky_relu"
+    assert ok(32, act) and ok(64, "relu", "tanh") and ok(32, act, "linear")
+    assert ok(32, act, use_edge_features=True, edge_width=1) and ok(64, act, use_edge_features=True, edge_width=64)
+    assert not ok(32, act, use_edge_features=True, edge_width=65)
+    assert not ok(32, act, use_edge_features=True, edge_width=0)
+    assert not ok(32, act, use_edge_features=True, edge_width=None)
+    for units in (4, 24, 36, 128, 200):
+        assert not ok(units, act)
+    assert not ok(32, "elu") and not ok(32, act, "softmax") and not ok(32, act, dtype="float64")
+    ro = afp.fused_attentive_readout_supported
+    assert ro(32) and ro(36, 0) and ro(200, 3, "mean") and ro(256, 2, "segment_sum") and ro(4)
+    assert not ro(2) and not ro(34) and not ro(260) and not ro(32, -1)
+    assert not ro(32, pooling_method="max") and not ro(32, pooling_method="nope")
+    assert not ro(32, activation="softmax") and not ro(32, dtype="float64")
+    # "elu" is a layer activation, not one of the older fused routes' codes
+    assert "elu" not in _ffi.ACTIVATION_CODES and _ffi.activation_code("elu") == _ffi.MP_ACT_ELU == 10
+
+
+def test_model_switch_and_served_blocks():
+    m = AttentiveFP.make_model()
+    assert m.fused_attentive_blocks == [True, True, True] and m.use_fused_attentive is True and m.auto_graph is True
+    assert len(m.attention_heads) == 2 and m.attention_heads[0].use_edge_features and \
+        not m.attention_heads[1].use_edge_features
+    m.use_fused_attentive = False
+    assert not any(lay.use_fused_attentive for lay in m.attentive_layers) and m.use_fused_attentive is False
+    m.use_fused_attentive = True
+    m.readout.use_fused_attentive = False
+    assert m.use_fused_attentive is False
+    paper = AttentiveFP.make_model(attention_args={"units": 200}, depthato=3)
+    assert paper.fused_attentive_blocks == [False, False, False, True]          # the heads serve 32 / 64, the readout 200
+    spec = [dict(s) for s in AttentiveFP.model_default["inputs"]]
+    spec[1]["shape"] = (None, 65)
+    assert AttentiveFP.make_model(inputs=spec).fused_attentive_blocks == [False, True, True]
+    node = AttentiveFP.make_model(output_embedding="node")
+    assert node.fused_attentive_blocks == [True, True] and node.readout is None
+    assert AttentiveFP.make_model(depthato=1).fused_attentive_blocks == [True, True]
+
+
+def test_new_symbols_in_header_and_table():
+    text = open(os.path.join(ROOT, "include", "mpengine.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    declared = set(re.findall(r"\b(mp_[a-z0-9_]+)\s*\(", text))
+    for name in NEW_SYMBOLS:
+        assert name in declared and name in _ffi.declared_symbols(), name
+        assert hasattr(_ffi.lib(), name), name
+
+
+def test_argument_errors_and_empty_problems():
+    lib = _ffi.lib()
+    edge = lambda u=32, n=4, d=3, e=0, act=7: lib.mp_afp_edge_f32(u, None, None, n, None, d, None, None, None, None, None,
+                                                                   None, None, None, e, None, act, 0.05, None, None, None)
+    assert edge() == _ffi.MP_OK                        # no edges: nothing to launch
+    assert edge(u=48) == _ffi.MP_EINVAL and b"mp_afp_edge_f32" in lib.mp_last_error()
+    assert edge(d=0) == _ffi.MP_EINVAL and edge(d=65) == _ffi.MP_EINVAL and edge(act=99) == _ffi.MP_EINVAL
+    assert edge(e=2 ** 31) == _ffi.MP_EINVAL and edge(e=3) == _ffi.MP_EINVAL
+    attend = lambda u=32, n=0, e=0, act=10: lib.mp_afp_attend_f32(u, None, None, n, None, e, None, None, act, 0.05, None,
+                                                                  None)
+    assert attend() == _ffi.MP_OK
+    assert attend(u=16) == _ffi.MP_EINVAL and attend(act=11) == _ffi.MP_EINVAL
+    assert attend(n=3) == _ffi.MP_EINVAL and b"mp_afp_attend_f32" in lib.mp_last_error()
+    ro = lambda n=0, g=0, u=32, depth=3, pool=0, act=7: lib.mp_afp_readout_f32(
+        None, None, n, None, g, u, depth, pool, None, None, None, None, None, None, act, 0.05, 10, 6, 5, None, None, None)
+    assert ro() == _ffi.MP_OK
+    assert ro(u=34) == _ffi.MP_EINVAL and ro(u=260) == _ffi.MP_EINVAL and ro(u=0) == _ffi.MP_EINVAL
+    assert ro(depth=-1) == _ffi.MP_EINVAL and ro(pool=_ffi.MP_MAX) == _ffi.MP_EINVAL and ro(act=99) == _ffi.MP_EINVAL
+    assert ro(g=2) == _ffi.MP_EINVAL and b"mp_afp_readout_f32" in lib.mp_last_error()
+    grad = lambda r=0, u=4, act=6: lib.mp_gru_combine_grad_f32(None, None, None, None, r, u, act, 5, None, None, None, None)
+    assert grad() == _ffi.MP_OK
+    assert grad(u=0) == _ffi.MP_EINVAL and grad(act=99) == _ffi.MP_EINVAL and grad(r=3) == _ffi.MP_EINVAL
+
+
+def test_synth_params_follow_the_model():
+    from gcnn_keras_amd import synth
+    model = AttentiveFP.make_model()
+    p = synth.attentivefp_params(model, seed=3)
+    assert [tuple(v.shape) for v in p.values()] == [tuple(t.shape) for _, t in model.weights]
+    assert all(v.dtype == np.float32 for v in p.values())
+    again = synth.attentivefp_params(model, seed=3)
+    assert all(np.array_equal(a, b) for a, b in zip(p.values(), again.values()))
+
+
+# ------------------------------------------------------------------------------------------ the GPU cases' own budget
+@pytest.mark.parametrize("name", sorted(aref.edge_cases()))
+def test_edge_cases_float32_restatement_inside_half_the_cap(name):
+    case = aref.edge_case(**aref.edge_cases()[name])
+    o32, l32 = aref.edge_restate(case, torch.float32)
+    o64, l64 = aref.edge_restate(case, torch.float64)
+    assert np.all(np.isfinite(o64)) and np.all(np.isfinite(o32))
+    assert rowwise_rel(o32, o64) <= BAR_CAP / 2
+    if l64.size:
+        assert max_rel(l32, l64) <= 2e-6
+    if name.startswith("x40"):
+        # the head's logit Dense reads activations, not raw features, so x40 gives tens, not hundreds: at 32 one float32
+        # ulp is 3.8e-6, above the 2e-6 bar on the logits - a U-term sum rounded per step in float32 does not pass
+        assert float(np.max(np.abs(l64))) > 32.0
+
+
+@pytest.mark.parametrize("name", sorted(aref.readout_cases()))
+def test_readout_cases_float32_restatement_inside_half_the_cap(name):
+    case = aref.readout_case(**aref.readout_cases()[name])
+    r32, r64 = aref.readout_restate(case, torch.float32), aref.readout_restate(case, torch.float64)
+    assert r64.shape == (aref.graph_rows(case["row_splits"]), case["u"]) and np.all(np.isfinite(r64))
+    assert rowwise_rel(r32, r64) <= BAR_CAP / 2
+
+
+def test_hub_case_has_the_shapes_it_claims():
+    import topologies as topo
+    case = aref.edge_case(**aref.edge_cases()["hub-shuffled-u64-d3-f64"])
+    deg = topo.in_degrees(case["flat"], case["rows"])
+    assert deg[0] == 0 and deg[-1] == 0 and set(aref.HUB_DEGREES) <= set(deg.tolist())
+    assert np.any(case["flat"][:, 0] == case["flat"][:, 1])                       # self loops
+    assert len(np.unique(case["flat"], axis=0)) < len(case["flat"])                # duplicate edges
+    assert np.any(np.diff(case["flat"][:, 0]) < 0)                                 # shuffled
+    assert np.all(np.diff(case["row_splits"]) >= 0) and 0 in np.diff(case["row_splits"])
+    lengths = np.diff(aref.readout_case(**aref.readout_cases()["tile-u32-d3-sum"])["row_splits"])
+    assert len(lengths) == 16 and {0, 1, 2, 63, 64, 65, 300} <= set(lengths.tolist())
+    peaked = aref.readout_case(**aref.readout_cases()["tile-u64-d3-mean-peaked"])
+    p = aref.params_to(peaked["params"], F64)
+    node = torch.tensor(peaked["nodes"], dtype=F64)
+    a = (node @ p["alpha/kernel"][64:])[peaked["row_splits"][6]:peaked["row_splits"][7], 0].numpy()   # the 300-node graph
+    w = np.exp(a - a.max())
+    assert (w / w.sum()).max() > 0.5                                                # one node takes most of the weight
