@@ -222,6 +222,11 @@ _SIGNATURES = {
     "mp_cmpnn_boost_f32": [P, P, c_int64, c_int64, P, P, c_int64, c_int, c_int, P, P],
     "mp_directed_edge_update_f32": [P, c_int64, P, P, c_int64, c_int64, P, P, P, P, c_int, c_int, c_float, P, P, P],
     "mp_gru_ragged_last_f32": [P, c_int64, P, c_int64, P, P, c_int64, c_int, c_int, P, P],
+    # DMPNN (csrc/mp_dmpnn.hip, csrc/mp_wgrad.hip): the reverse of mp_directed_edge_update_f32
+    "mp_directed_edge_update_grad_f32": [P, P, c_int64, c_int64, P, c_int, P, P, P],
+    "mp_directed_edge_wgrad_ws_bytes": [c_int64, c_int64, P],
+    "mp_directed_edge_wgrad_f32": [P, c_int64, P, c_int64, c_int64, P, P, P, P, P, P, c_size_t, P, P],
+    "mp_directed_edge_hgrad_f32": [P, c_int64, P, c_int64, c_int64, P, P, P, P, P, P],
     # one RGCN block (kgcnn/literature/RGCN.py:96-103) or one GNNFilm block (kgcnn/literature/GNNFilm.py:93-102)
     "mp_relational_conv_f32": [c_int, P, c_int64, c_int64, P, c_int64, P, P, P, P, c_int64, P, P, c_int64, P, P, c_int,
                                P, P, P, P, c_int, c_int, c_float, P, P],

@@ -1212,3 +1212,32 @@ class GRUCombine(torch.autograd.Function):
                       int(h.shape[0]), int(h.shape[1]), ctx.act, ctx.rec_act, _ffi.ptr(d_mx), _ffi.ptr(d_mh),
                       _ffi.ptr(d_h), _ffi.stream())
         return d_mx, d_mh, d_h, None, None
+
+
+# -------------------------------------------------------------------------------------------------------------- DMPNN
+# First-order rule of the fused DMPNN round (layers/conv/dmpnn_conv.py DMPNNStep; csrc/mp_dmpnn.hip, csrc/mp_wgrad.hip).
+# Unlike the EGNN edge step it returns the gradients of its weights, so the layer records it when the shared Dense trains.
+
+class DirectedEdgeUpdate(torch.autograd.Function):
+    """One fused DMPNN round, ``y = act2((R[send] - h[rev]) W + b + h0)`` with ``R`` the receiver sum of ``h``
+    (``spec``: layers/conv/dmpnn_conv.py ``DirectedStepSpec``).  The forward is the fused route's two launches and saves
+    ``R``, ``h`` and the output ``y``; the backward is csrc/mp_dmpnn.hip and the gathered-difference weight gradient of
+    csrc/mp_wgrad.hip: ``h_bar``, ``h0_bar``, ``W_bar`` and ``b_bar``, each only when asked.  First order."""
+
+    @staticmethod
+    def forward(ctx, h, h0, kernel, bias, spec):
+        hv = h.detach().contiguous()
+        r, y = spec.forward(hv, h0.detach().contiguous(), kernel.detach(), None if bias is None else bias.detach())
+        ctx.spec = spec
+        ctx.save_for_backward(r, hv, y, kernel)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        r, hv, y, kernel = ctx.saved_tensors
+        want_h, want_h0 = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        want_w = ctx.needs_input_grad[2] and not _input_grads_only[0]
+        want_b = ctx.needs_input_grad[3] and not _input_grads_only[0]
+        h_bar, p, w_bar, b_bar = ctx.spec.grad(r, hv, y, kernel.detach(), g.contiguous(), want_h, want_w, want_b)
+        return h_bar, (p if want_h0 else None), w_bar, b_bar, None

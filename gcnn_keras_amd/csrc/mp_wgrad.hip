@@ -4,6 +4,8 @@
 //   mp_dense_wgrad_f32        dW (K,U) = X^T G and db (U) = sum_r G[r] over R rows
 //   mp_embedding_grad_f32     dTable[t] = sum_{i: number_i = t} G[i], node order within each type
 //   mp_softmax_rows_grad_f32  out = y * (g - rowsum(g * y))
+//   mp_directed_edge_wgrad_f32  mp_dense_wgrad_f32 whose X is the gathered difference h[send] - he[rev] of the directed
+//                             edge update (kgcnn/literature/DMPNN.py:137-138), formed while a slab is staged
 //
 // Weight gradient: the reduction runs over the ROWS of x and g, so the MFMA's k dimension is the row index.  Both
 // operands are k-contiguous in HBM in the wrong direction for a register load (x is (R,K) row-major), so a workgroup
@@ -36,6 +38,12 @@ struct WgradArgs {
   float* dw;        // (K, U) destination of this launch (the final dW or the chunk's slab base)
   float* db;        // (U) destination of the bias sum (final db or the bias slab base), null: no bias
   int64_t dw_stride, db_stride;   // per-chunk stride of the slabs (0 when there is one chunk)
+  // DIFF (mp_directed_edge_wgrad_f32): row r of x is x[send[r]] - x2[rev[r]], formed while the slab is staged
+  const float* x2;        // (R, K), rows read at rev; a row with rev < 0 counts as zero
+  const int32_t* send;    // (R) rows of x, inside [0, xrows) or clamped and flagged
+  const int32_t* rev;     // (R) rows of x2, below R or clamped and flagged
+  int64_t xrows;
+  int32_t* flags;         // nullable
 };
 
 // Upper bound on the chunk count, non-decreasing in R (the workspace size is derived from it).
@@ -59,8 +67,11 @@ inline void plan_chunks(int64_t R, int64_t K, int64_t U, int64_t* rows_per_chunk
 // VEC: K % 4 == 0, U % 4 == 0 and 16-B aligned operands (16-B loads); the scalar path covers odd shapes (GCN's 1433
 // input features, 7-class heads, U = 1).  Loads are unconditional from clamped addresses; what lies outside the chunk /
 // the matrix is zeroed when the registers are written to LDS (rows beyond the chunk must be 0 in G for the bias sum).
-template <bool VEC>
+// DIFF (VEC only): the A operand is a gathered difference, x[send[r]] - x2[rev[r]] (the directed edge update's input,
+// csrc/mp_cmpnn.hip), never written to memory: a slab's row indices are read one slab ahead of its rows.
+template <bool VEC, bool DIFF = false>
 __global__ __launch_bounds__(256) void dense_wgrad_kernel(WgradArgs a) {
+  static_assert(VEC || !DIFF, "the gathered difference is built for the 16-byte path");
   __shared__ __align__(16) float Xs[BR * LDW];
   __shared__ __align__(16) float Gs[BR * LDW];
   const int tid = threadIdx.x;
@@ -87,6 +98,25 @@ __global__ __launch_bounds__(256) void dense_wgrad_kernel(WgradArgs a) {
   constexpr int NS = (BR * WT) / 256;         // floats per thread and tile, scalar path
   float4 rx4[VEC ? NV : 1], rg4[VEC ? NV : 1];
   float rx[VEC ? 1 : NS], rg[VEC ? 1 : NS];
+  float4 rx2[DIFF ? NV : 1];                       // the reverse rows of the difference
+  int32_t is[DIFF ? NV : 1], ir[DIFF ? NV : 1];    // sender and reverse row of the NEXT slab to load
+  int local_flags = 0;
+
+  auto load_index = [&](int64_t r0) {
+    if constexpr (DIFF) {
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        int64_t gr = r0 + (tid + i * 256) / (WT / 4);
+        const bool live = gr < rend;
+        gr = gr < R ? gr : R - 1;
+        int32_t s = a.send[gr], r = a.rev[gr];
+        if (s < 0 || s >= a.xrows) { if (live) local_flags |= MP_FLAG_OOB; s = s < 0 ? 0 : static_cast<int32_t>(a.xrows - 1); }
+        if (r >= R) { if (live) local_flags |= MP_FLAG_OOB; r = static_cast<int32_t>(R - 1); }
+        is[i] = s;
+        ir[i] = r;
+      }
+    }
+  };
 
   auto load_tile = [&](int64_t r0) {
     if constexpr (VEC) {
@@ -98,7 +128,14 @@ __global__ __launch_bounds__(256) void dense_wgrad_kernel(WgradArgs a) {
         gr = gr < R ? gr : R - 1;
         gk = gk < K ? gk : K - 4;
         gu = gu < U ? gu : U - 4;
-        rx4[i] = *reinterpret_cast<const float4*>(a.x + gr * K + gk);
+        if constexpr (DIFF) {
+          rx4[i] = *reinterpret_cast<const float4*>(a.x + static_cast<int64_t>(is[i]) * K + gk);
+          rx2[i] = *reinterpret_cast<const float4*>(a.x2 + static_cast<int64_t>(ir[i] < 0 ? 0 : ir[i]) * K + gk);
+          if (ir[i] < 0) rx2[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+          rx4[i] = make_float4(rx4[i].x - rx2[i].x, rx4[i].y - rx2[i].y, rx4[i].z - rx2[i].z, rx4[i].w - rx2[i].w);
+        } else {
+          rx4[i] = *reinterpret_cast<const float4*>(a.x + gr * K + gk);
+        }
         rg4[i] = *reinterpret_cast<const float4*>(a.g + gr * U + gu);
       }
     } else {
@@ -123,8 +160,17 @@ __global__ __launch_bounds__(256) void dense_wgrad_kernel(WgradArgs a) {
         const int idx = tid + i * 256;
         const int r = idx / (WT / 4), c = (idx % (WT / 4)) * 4;
         const bool row_ok = (r0 + r) < rend;
-        *reinterpret_cast<float4*>(Xs + r * LDW + c) = (row_ok && (k0 + c) < K) ? rx4[i] : z4;
-        *reinterpret_cast<float4*>(Gs + r * LDW + c) = (row_ok && (u0 + c) < U) ? rg4[i] : z4;
+        if constexpr (DIFF) {   // selects on the values: a select between the two arrays' addresses costs a stack slot
+          const bool okx = row_ok && (k0 + c) < K, okg = row_ok && (u0 + c) < U;
+          const float4 vx = rx4[i], vg = rg4[i];
+          *reinterpret_cast<float4*>(Xs + r * LDW + c) =
+              make_float4(okx ? vx.x : 0.f, okx ? vx.y : 0.f, okx ? vx.z : 0.f, okx ? vx.w : 0.f);
+          *reinterpret_cast<float4*>(Gs + r * LDW + c) =
+              make_float4(okg ? vg.x : 0.f, okg ? vg.y : 0.f, okg ? vg.z : 0.f, okg ? vg.w : 0.f);
+        } else {
+          *reinterpret_cast<float4*>(Xs + r * LDW + c) = (row_ok && (k0 + c) < K) ? rx4[i] : z4;
+          *reinterpret_cast<float4*>(Gs + r * LDW + c) = (row_ok && (u0 + c) < U) ? rg4[i] : z4;
+        }
       }
     } else {
 #pragma unroll
@@ -138,7 +184,11 @@ __global__ __launch_bounds__(256) void dense_wgrad_kernel(WgradArgs a) {
     }
   };
 
-  if (stages > 0) load_tile(rbeg);
+  if (stages > 0) {
+    load_index(rbeg);
+    load_tile(rbeg);
+    if (stages > 1) load_index(rbeg + BR);
+  }
   const int col = lane & 15, quad = lane >> 4;
   const float* xa = Xs + quad * LDW + wk * 32 + col;
   const float* gb = Gs + quad * LDW + wu * 32 + col;
@@ -146,7 +196,10 @@ __global__ __launch_bounds__(256) void dense_wgrad_kernel(WgradArgs a) {
     const int64_t r0 = rbeg + s * BR;
     store_tile(r0);
     __syncthreads();
-    if (s + 1 < stages) load_tile(r0 + BR);   // next slab's loads in flight under this slab's MFMAs
+    if (s + 1 < stages) {
+      load_tile(r0 + BR);   // next slab's loads in flight under this slab's MFMAs
+      if (s + 2 < stages) load_index(r0 + 2 * BR);
+    }
 #pragma unroll
     for (int kk = 0; kk < BR / 4; ++kk) {
       const float a0 = xa[kk * 4 * LDW], a1 = xa[kk * 4 * LDW + 16];
@@ -179,6 +232,9 @@ __global__ __launch_bounds__(256) void dense_wgrad_kernel(WgradArgs a) {
     }
   }
   if (do_bias && wave == 0 && u0 + lane < U) a.db[chunk * a.db_stride + u0 + lane] = bsum;
+  if constexpr (DIFF) {
+    if (a.flags != nullptr && blockIdx.y == 0 && blockIdx.z == 0) mp_publish_flags(a.flags, local_flags);
+  }
 }
 
 // dW = sum_c slab[c], db = sum_c bslab[c], chunks added in order (fixed): the bits do not depend on scheduling.  One
@@ -249,30 +305,33 @@ int mp_dense_wgrad_ws_bytes(int64_t R, int64_t K, int64_t U, size_t* bytes_out_h
   return MP_OK;
 }
 
-int mp_dense_wgrad_f32(const float* x, int64_t R, int64_t K, const float* g, int64_t U, float* dw, float* db, void* ws,
-                       size_t ws_bytes, mpStream_t stream) {
-  MP_REQUIRE(R >= 0 && K >= 1 && U >= 1, "mp_dense_wgrad_f32: bad sizes R=%lld K=%lld U=%lld", (long long)R,
-             (long long)K, (long long)U);
-  MP_REQUIRE(dw, "mp_dense_wgrad_f32: null dW");
+// Both entry points: the row split, the launch and the in-order reduction.  `diff` selects the gathered-difference A
+// operand (a.x2 / a.send / a.rev / a.xrows / a.flags are set by the caller).
+static int wgrad_launch(const char* what, WgradArgs a, bool diff, void* ws, size_t ws_bytes, mpStream_t stream) {
+  const float* x = a.x;
+  const float* g = a.g;
+  const int64_t R = a.R, K = a.K, U = a.U;
+  float* dw = a.dw;
+  float* db = a.db;
   hipStream_t s = mp::as_stream(stream);
   if (R == 0) {   // empty sum
     MP_HIP(hipMemsetAsync(dw, 0, sizeof(float) * static_cast<size_t>(K * U), s));
     if (db) MP_HIP(hipMemsetAsync(db, 0, sizeof(float) * static_cast<size_t>(U), s));
     return MP_OK;
   }
-  MP_REQUIRE(x && g, "mp_dense_wgrad_f32: null pointer");
+  MP_REQUIRE(x && g, "%s: null pointer", what);
   const int64_t gk = mp::ceil_div(K, WT), gu = mp::ceil_div(U, WT);
-  MP_REQUIRE(gk <= 65535 && gu <= 65535, "mp_dense_wgrad_f32: K or U too large");
+  MP_REQUIRE(gk <= 65535 && gu <= 65535, "%s: K or U too large", what);
   int64_t rows_per_chunk = 0, chunks = 0;
   plan_chunks(R, K, U, &rows_per_chunk, &chunks);
-  WgradArgs a{x, g, R, K, U, rows_per_chunk, dw, db, 0, 0};
+  a.rows_per_chunk = rows_per_chunk;
   float* slab = nullptr;
   float* bslab = nullptr;
   if (chunks > 1) {
     size_t need = 0;
     int rc = mp_dense_wgrad_ws_bytes(R, K, U, &need);
     if (rc != MP_OK) return rc;
-    MP_REQUIRE(ws && ws_bytes >= need, "mp_dense_wgrad_f32: workspace %zu < %zu bytes", ws_bytes, need);
+    MP_REQUIRE(ws && ws_bytes >= need, "%s: workspace %zu < %zu bytes", what, ws_bytes, need);
     slab = static_cast<float*>(ws);
     bslab = slab + chunks * K * U;
     a.dw = slab;
@@ -283,13 +342,48 @@ int mp_dense_wgrad_f32(const float* x, int64_t R, int64_t K, const float* g, int
   const bool vec = (K % 4 == 0) && (U % 4 == 0) && (reinterpret_cast<uintptr_t>(x) % 16 == 0) &&
                    (reinterpret_cast<uintptr_t>(g) % 16 == 0);
   dim3 grid(static_cast<unsigned>(chunks), static_cast<unsigned>(gk), static_cast<unsigned>(gu));
-  if (vec) dense_wgrad_kernel<true><<<grid, 256, 0, s>>>(a);
-  else dense_wgrad_kernel<false><<<grid, 256, 0, s>>>(a);
-  int rc = mp::check_launch("mp_dense_wgrad_f32");
+  if (diff) {
+    MP_REQUIRE(vec, "%s: widths are multiples of 4 and operands 16-byte aligned", what);
+    dense_wgrad_kernel<true, true><<<grid, 256, 0, s>>>(a);
+  } else if (vec) {
+    dense_wgrad_kernel<true><<<grid, 256, 0, s>>>(a);
+  } else {
+    dense_wgrad_kernel<false><<<grid, 256, 0, s>>>(a);
+  }
+  int rc = mp::check_launch(what);
   if (rc != MP_OK || chunks == 1) return rc;
   wgrad_reduce_kernel<<<mp::grid_for(K * U + (db ? U : 0), REDUCE_BLOCK), REDUCE_BLOCK, 0, s>>>(slab, bslab, chunks,
                                                                                               K * U, U, dw, db);
-  return mp::check_launch("mp_dense_wgrad_f32 (reduce)");
+  return mp::check_launch(what);
+}
+
+int mp_dense_wgrad_f32(const float* x, int64_t R, int64_t K, const float* g, int64_t U, float* dw, float* db, void* ws,
+                       size_t ws_bytes, mpStream_t stream) {
+  MP_REQUIRE(R >= 0 && K >= 1 && U >= 1, "mp_dense_wgrad_f32: bad sizes R=%lld K=%lld U=%lld", (long long)R,
+             (long long)K, (long long)U);
+  MP_REQUIRE(dw, "mp_dense_wgrad_f32: null dW");
+  WgradArgs a{x, g, R, K, U, 0, dw, db, 0, 0, nullptr, nullptr, nullptr, 0, nullptr};
+  return wgrad_launch("mp_dense_wgrad_f32", a, false, ws, ws_bytes, stream);
+}
+
+int mp_directed_edge_wgrad_ws_bytes(int64_t E, int64_t F, size_t* bytes_out_host) {
+  MP_REQUIRE(E >= 0 && F >= 4 && F % 4 == 0 && bytes_out_host, "mp_directed_edge_wgrad_ws_bytes: bad arguments");
+  return mp_dense_wgrad_ws_bytes(E, F, F, bytes_out_host);
+}
+
+int mp_directed_edge_wgrad_f32(const float* h, int64_t N, const float* he, int64_t E, int64_t F, const int32_t* send,
+                               const int32_t* rev, const float* p, float* dw, float* db, void* ws, size_t ws_bytes,
+                               int32_t* flags, mpStream_t stream) {
+  const char* what = "mp_directed_edge_wgrad_f32";
+  MP_REQUIRE(N >= 0 && E >= 0 && F >= 4 && F % 4 == 0, "%s: bad sizes N=%lld E=%lld F=%lld (F a multiple of 4)", what,
+             (long long)N, (long long)E, (long long)F);
+  MP_REQUIRE(N < (int64_t{1} << 31) - 1 && E < (int64_t{1} << 31) - 1, "%s: nodes and edges are indexed with 32 bits",
+             what);
+  MP_REQUIRE(dw, "%s: null dW", what);
+  MP_REQUIRE(E == 0 || (h && he && send && rev && p && N > 0), "%s: null pointer, or edges and no node", what);
+  MP_REQUIRE(mp::aligned16(h) && mp::aligned16(he) && mp::aligned16(p), "%s: operands must be 16-byte aligned", what);
+  WgradArgs a{h, p, E, F, F, 0, dw, db, 0, 0, he, send, rev, N, flags};
+  return wgrad_launch(what, a, true, ws, ws_bytes, stream);
 }
 
 int mp_softmax_rows_grad_f32(const float* y, const float* g, int64_t R, int64_t C, float* out, mpStream_t stream) {

@@ -4,14 +4,20 @@ Edge states start as ``Dense([n_j || e_ij])``; each of ``depth`` rounds replaces
 ``act(Dense(sum of the states arriving at its sender, minus its reverse edge) + h0)``
 (``DMPNNPPoolingEdgesDirected``); nodes then read ``Dense([sum of incoming states || n])``.
 The optional graph-state input of the reference is not wired (no BASELINE config uses it).
+
+A round is one ``DMPNNStep`` (``layers/conv/dmpnn_conv.py``) around the one shared ``Dense(**edge_dense)``.  Rounds whose
+sizes fit take two launches (the receiver sum, then the fused directed edge update of csrc/mp_cmpnn.hip), with and without
+a tape: ``compile`` / ``train_on_batch`` / ``fit`` record ``autograd.DirectedEdgeUpdate``, whose backward is
+csrc/mp_dmpnn.hip.  ``model.fused_step_rounds`` lists which rounds are served, ``model.use_fused_step`` (or
+``round.use_fused_step``) switches the route.  ``Dropout`` is the identity.
 """
 from ..layers.casting import ChangeTensorType
-from ..layers.conv.dmpnn_conv import DMPNNPPoolingEdgesDirected
+from ..layers.conv.dmpnn_conv import DMPNNStep
 from ..layers.gather import GatherNodesOutgoing
 from ..layers.mlp import MLP, GraphMLP
-from ..layers.modules import Activation, Dense, Dropout, LazyAdd, LazyConcatenate, OptionalInputEmbedding
+from ..layers.modules import Activation, Dense, Dropout, LazyConcatenate, OptionalInputEmbedding
 from ..layers.pooling import PoolingLocalEdges, PoolingNodes
-from ..model.utils import Model, update_model_kwargs
+from ..model.utils import RouteSwitchModel, update_model_kwargs
 
 __model_version__ = "2022.11.25"
 
@@ -38,6 +44,14 @@ model_default = {
 }
 
 
+class _DmpnnModel(RouteSwitchModel):
+    """``Model`` with the ``use_fused_step`` switch over all rounds."""
+
+    switch_attr, switch_layers_attr = "use_fused_step", "step_layers"
+    step_layers = ()
+    use_fused_step = RouteSwitchModel.switch
+
+
 def _width(spec, embedding):
     return embedding["output_dim"] if len(spec["shape"]) < 2 else spec["shape"][-1]
 
@@ -61,8 +75,8 @@ def make_model(name: str = None, inputs: list = None, input_embedding: dict = No
     concat = LazyConcatenate(axis=-1)
     dense_h0 = Dense(**edge_initialize)
     dense_edge = Dense(**edge_dense)                      # one layer shared by all rounds, like the reference
-    pool_directed = [DMPNNPPoolingEdgesDirected() for _ in range(depth)]
-    add, act = LazyAdd(), Activation(**edge_activation)
+    act = Activation(**edge_activation)
+    steps = [DMPNNStep(dense=dense_edge, activation=act) for _ in range(depth)]   # around the shared layers
     drop = Dropout(**dropout) if dropout is not None else None
     pool_edges = PoolingLocalEdges(**pooling_args)
     dense_node = Dense(**node_dense)
@@ -76,8 +90,8 @@ def make_model(name: str = None, inputs: list = None, input_embedding: dict = No
         n, ed = embed_n(node_input), embed_e(edge_input)
         h0 = dense_h0(concat([gather_out([n, edi]), ed]))
         h = h0
-        for lay in pool_directed:
-            h = act(add([dense_edge(lay([n, h, edi, ed_pairs])), h0]))
+        for lay in steps:
+            h = lay([n, h, h0, edi, ed_pairs])
             if drop is not None:
                 h = drop(h)
         hv = dense_node(concat([pool_edges([n, h, edi]), n]))
@@ -91,11 +105,18 @@ def make_model(name: str = None, inputs: list = None, input_embedding: dict = No
     embed_e.ensure_built((None, None))
     dense_h0.ensure_built((None, None, node_width + edge_width))
     dense_edge.ensure_built((None, None, edge_initialize["units"]))
+    for lay in steps:
+        lay.ensure_built([(None, None, node_width), (None, None, edge_initialize["units"]),
+                          (None, None, edge_initialize["units"]), (None, None, 2), (None, None, 1)])
     dense_node.ensure_built((None, None, edge_dense["units"] + node_width))
     out_mlp.ensure_built((None, node_dense["units"]) if output_embedding == "graph" else (None, None, node_dense["units"]))
-    model = Model(name, forward, [embed_n, embed_e, dense_h0, dense_edge, dense_node, out_mlp],
-                  config={"depth": depth, "edge_initialize": edge_initialize, "edge_dense": edge_dense,
-                          "node_dense": node_dense})
+    # the rounds hold no weights of their own: the weight list and its order stay (embeddings, h0 Dense, edge Dense, ...)
+    model = _DmpnnModel(name, forward, [embed_n, embed_e, dense_h0, dense_edge, dense_node, out_mlp],
+                        config={"depth": depth, "edge_initialize": edge_initialize, "edge_dense": edge_dense,
+                                "node_dense": node_dense})
     model.__kgcnn_model_version__ = __model_version__
-    model.auto_graph = True   # re-bound inputs replay the whole layer sequence from one HIP graph (model/utils.py)
+    model.step_layers = steps
+    model.fused_step_rounds = [bool(lay.fused_step) for lay in steps]
+    # re-bound inputs replay the whole forward from one HIP graph (model/utils.py); the route is part of its identity
+    model.auto_graph = True
     return model
