@@ -235,6 +235,11 @@ _SIGNATURES = {
     "mp_afp_attend_f32": [c_int, P, P, c_int64, P, c_int64, P, P, c_int, c_float, P, P],
     "mp_afp_readout_f32": [P, P, c_int64, P, c_int64, c_int, c_int, c_int, P, P, P, P, P, P, c_int, c_float, c_int, c_int,
                            c_int, P, P, P],
+    # MEGAN (csrc/mp_megan.hip): the importance readout behind the last attention layer, and its reverse
+    "mp_megan_edge_importance_f32": [c_int, P, c_int64, c_int, P, P],
+    "mp_megan_readout_f32": [P, c_int64, c_int, P, P, P, P, P, P, c_int64, c_int64, P, c_int64, c_int, P, P, P, P],
+    "mp_megan_readout_grad_f32": [P, P, P, P, P, c_int64, c_int, c_int64, P, c_int64, c_int, P, P, P, P],
+    "mp_megan_edge_importance_grad_f32": [P, P, P, P, P, P, c_int64, c_int64, c_int, P, P],
     "mp_scaler_species_count": [P, c_int, P, c_int64, c_int64, P, P, P, P, P],
     "mp_scaler_fit_ws_bytes": [c_int64, c_int, P],
     "mp_scaler_normal_f64": [P, P, c_int64, P, c_int, c_int, P, c_double, c_int, P, P, P, P, c_size_t, P],

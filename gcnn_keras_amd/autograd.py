@@ -1241,3 +1241,87 @@ class DirectedEdgeUpdate(torch.autograd.Function):
         want_b = ctx.needs_input_grad[3] and not _input_grads_only[0]
         h_bar, p, w_bar, b_bar = ctx.spec.grad(r, hv, y, kernel.detach(), g.contiguous(), want_h, want_w, want_b)
         return h_bar, (p if want_h0 else None), w_bar, b_bar, None
+
+
+# -------------------------------------------------------------------------------------------------------------- MEGAN
+# First-order rule of the fused importance readout (literature/MEGAN.py; csrc/mp_megan.hip): two launches forward, two
+# in reverse, whatever the number of channels and attention layers.
+
+MEGAN_READOUT_SIZES = {"max_channels": 8, "max_layers": 8, "max_width": 512}   # include/mpengine.h MP_MEGAN_*
+
+
+def megan_readout_values(x, z, plan, row_splits, g_rows, op, logits, want_p=False):
+    """The two forward launches on detached, contiguous operands: ``(out (G, K W), ni (N, K), ei (M, K), p or None)``."""
+    import ctypes
+    n, w = int(x.shape[0]), int(x.shape[1])
+    k = int(z.shape[1])
+    m = plan.M
+    if plan.K != 2 or plan.N != n:
+        raise ValueError("the MEGAN readout takes (batch, [M], 2) indices over the %d nodes, got K=%d over %d nodes"
+                         % (n, plan.K, plan.N))
+    for t in logits:
+        if t.numel() != m * k:
+            raise ValueError("the MEGAN readout: attention logits of %d elements for %d edges and %d channels"
+                             % (t.numel(), m, k))
+    dev = x.device
+    ei = torch.empty((m, k), dtype=torch.float32, device=dev)
+    ni = torch.empty((n, k), dtype=torch.float32, device=dev)
+    out = torch.empty((g_rows, k * w), dtype=torch.float32, device=dev)
+    p = torch.empty((n, k), dtype=torch.float32, device=dev) if want_p else None
+    ptr0, perm0, _ = plan.csr(0)
+    ptr1, perm1, _ = plan.csr(1)
+    group = (ctypes.c_void_p * len(logits))(*[_ffi.ptr(t).value for t in logits])
+    _ffi.call("mp_megan_edge_importance_f32", len(logits), group, m, k, _ffi.ptr(ei), _ffi.stream())
+    _ffi.call("mp_megan_readout_f32", _ffi.ptr(ei), m, k, _ffi.ptr(ptr0), _ffi.ptr(perm0), _ffi.ptr(ptr1),
+              _ffi.ptr(perm1), _ffi.ptr(z), _ffi.ptr(x), n, w, _ffi.ptr(row_splits), g_rows, op, _ffi.ptr(p),
+              _ffi.ptr(ni), _ffi.ptr(out), _ffi.stream())
+    return out, ni, ei, p
+
+
+class MeganReadout(torch.autograd.Function):
+    """MEGAN's importance readout: from the node embeddings ``x`` (N, W), the linear output ``z`` (N, K) of the
+    node-importance Dense chain and the ``L`` attention-logit tensors (M, K[, 1]) to ``(out (G, K W), node importances
+    (N, K), edge importances (M, K))``.  The forward saves ``x``, ``z``, the pooled edge importances ``p`` and ``ei``;
+    the backward is ``mp_megan_readout_grad_f32`` and ``mp_megan_edge_importance_grad_f32``: ``x_bar``, ``z_bar`` and
+    one ``s_bar`` that is the gradient of every logit tensor.  First order."""
+
+    @staticmethod
+    def forward(ctx, x, z, plan, row_splits, g_rows, op, *logits):
+        xc, zc = x.detach().contiguous(), z.detach().contiguous()
+        lc = [t.detach().contiguous() for t in logits]
+        out, ni, ei, p = megan_readout_values(xc, zc, plan, row_splits, g_rows, op, lc, want_p=True)
+        ctx.plan, ctx.splits, ctx.g, ctx.op = plan, row_splits, g_rows, op
+        ctx.logit_shapes = [tuple(t.shape) for t in logits]
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(xc, zc, p, ei)
+        return out, ni, ei
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out, g_ni, g_ei):
+        x, z, p, ei = ctx.saved_tensors
+        n, w = int(x.shape[0]), int(x.shape[1])
+        m, k = int(ei.shape[0]), int(ei.shape[1])
+        plan = ctx.plan
+        dev = x.device
+        if g_out is None:
+            g_out = torch.zeros((ctx.g, k * w), dtype=torch.float32, device=dev)
+        g_out = g_out.contiguous()
+        g_ni = None if g_ni is None else g_ni.contiguous()
+        g_ei = None if g_ei is None else g_ei.contiguous()
+        x_bar = torch.empty_like(x)
+        z_bar = torch.empty_like(z)
+        q = torch.empty_like(z)
+        _ffi.call("mp_megan_readout_grad_f32", _ffi.ptr(g_out), _ffi.ptr(g_ni), _ffi.ptr(x), _ffi.ptr(z), _ffi.ptr(p), n,
+                  k, w, _ffi.ptr(ctx.splits), ctx.g, ctx.op, _ffi.ptr(x_bar), _ffi.ptr(z_bar), _ffi.ptr(q), _ffi.stream())
+        s_bars = [None] * len(ctx.logit_shapes)
+        if any(ctx.needs_input_grad[6:]):
+            ptr0, _, _ = plan.csr(0)
+            ptr1, _, _ = plan.csr(1)
+            s_bar = torch.empty_like(ei)
+            _ffi.call("mp_megan_edge_importance_grad_f32", _ffi.ptr(g_ei), _ffi.ptr(q), _ffi.ptr(ei), _ffi.ptr(plan.cols),
+                      _ffi.ptr(ptr0), _ffi.ptr(ptr1), n, m, k, _ffi.ptr(s_bar), _ffi.stream())
+            s_bars = [s_bar.view(shape) if want else None
+                      for shape, want in zip(ctx.logit_shapes, ctx.needs_input_grad[6:])]
+        return (x_bar if ctx.needs_input_grad[0] else None, z_bar if ctx.needs_input_grad[1] else None, None, None, None,
+                None) + tuple(s_bars)

@@ -774,3 +774,23 @@ def relational_params(model, seed=43, dense_scale=1.0):
             v = dense_scale * glorot_uniform(rng, shape[-2], shape[-1], shape=shape)
         p["%03d/%s" % (i, name)] = np.asarray(v, dtype=np.float32)
     return p
+
+
+def megan_batch(num_graphs=128, seed=1234, node_features=12, edge_features=6, **kwargs):
+    """MEGAN inputs on the :func:`qm9_like_batch` graphs (``kwargs`` go there): additionally ``node_attributes``
+    ``(N, node_features)`` and ``edge_attributes`` ``(M, edge_features)``, float32 ``N(0, 1)`` from a stream of their own
+    (``seed + 2``), and ``node_type`` ``(N,)`` float32 numbers in ``[0, 95)`` for an embedding input."""
+    b = qm9_like_batch(num_graphs=num_graphs, seed=seed, **kwargs)
+    rng = np.random.default_rng(seed + 2)
+    n, m = int(b["node_splits"][-1]), int(b["edge_splits"][-1])
+    b["node_attributes"] = rng.normal(size=(n, node_features)).astype(np.float32)
+    b["edge_attributes"] = rng.normal(size=(m, edge_features)).astype(np.float32)
+    b["node_type"] = rng.integers(0, 95, size=n).astype(np.float32)
+    return b
+
+
+def megan_params(model, seed=53, dense_scale=1.0):
+    """Random weights for a built MEGAN ``model`` in ``model.weights`` order: kernels Glorot-uniform times ``dense_scale``,
+    biases in +-0.1, embeddings in +-0.5.  At scale 1 the summed attention logits stay of order 1, so the edge
+    importances do not saturate."""
+    return relational_params(model, seed=seed, dense_scale=dense_scale)
