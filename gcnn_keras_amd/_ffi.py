@@ -29,6 +29,11 @@ MP_PERIODIC_FLAG_CAPACITY, MP_PERIODIC_FLAG_IMAGE_RANGE, MP_PERIODIC_FLAG_SINGUL
 MP_CMPNN_EDGE_TILE, MP_GRU_RAGGED_MAX_UNITS = 64, 512   # include/mpengine.h
 MP_GAT_V1, MP_GAT_V2, MP_GAT_MAX_HEADS = 0, 1, 8   # include/mpengine.h
 MP_RELCONV_RGCN, MP_RELCONV_FILM, MP_RELCONV_MAX_RELATIONS = 0, 1, 64   # include/mpengine.h
+# include/mpengine.h: tiles, distance trafos, merges and epilogue caps of mp_mat_attention_f32
+MP_MAT_RECV_TILE, MP_MAT_SEND_TILE = 16, 64
+MP_MAT_TRAFO_NONE, MP_MAT_TRAFO_EXP, MP_MAT_TRAFO_SOFTMAX = 0, 1, 2
+MP_MAT_MERGE_CONCAT, MP_MAT_MERGE_SUM = 0, 1
+MP_MAT_EPILOGUE_MAX_CHANNELS, MP_MAT_EPILOGUE_MAX_WIDTH = 256, 256
 
 ACTIVATION_CODES = {
     None: 0, "linear": 0, "relu": 1, "kgcnn>shifted_softplus": 2, "shifted_softplus": 2, "softplus": 3,
@@ -240,6 +245,9 @@ _SIGNATURES = {
     "mp_megan_readout_f32": [P, c_int64, c_int, P, P, P, P, P, P, c_int64, c_int64, P, c_int64, c_int, P, P, P, P],
     "mp_megan_readout_grad_f32": [P, P, P, P, P, c_int64, c_int, c_int64, P, c_int64, c_int, P, P, P, P],
     "mp_megan_edge_importance_grad_f32": [P, P, P, P, P, P, c_int64, c_int64, c_int, P, P],
+    # MAT (csrc/mp_mat.hip): all-pairs molecule attention on ragged rows, optional merge + residual epilogue
+    "mp_mat_attention_f32": [P, c_int64, P, c_int64, P, c_int64, c_int64, c_int, c_int, P, P, c_int64, P, P, P, P, c_int64,
+                             c_int, c_float, c_float, c_float, c_int, P, c_int64, c_int, P, P, P, P],
     "mp_scaler_species_count": [P, c_int, P, c_int64, c_int64, P, P, P, P, P],
     "mp_scaler_fit_ws_bytes": [c_int64, c_int, P],
     "mp_scaler_normal_f64": [P, P, c_int64, P, c_int, c_int, P, c_double, c_int, P, P, P, P, c_size_t, P],

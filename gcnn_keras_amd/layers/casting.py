@@ -66,3 +66,49 @@ class ChangeTensorType(GraphBaseLayer):
                        "output_tensor_type": self.output_tensor_type, "shape": self.shape,
                        "default_value": self.default_value, "boolean_mask": self.boolean_mask})
         return config
+
+
+class CastEdgeIndicesToDenseAdjacency(GraphBaseLayer):
+    """Ragged ``[nodes, edges, indices]`` -> padded adjacency ``(batch, N_max, N_max, F...)`` and mask ``(batch, N_max,
+    N_max)`` by scatter-ADD of the edge values, so duplicate edges add (mirror of kgcnn/layers/casting.py:105-196).
+    Compatibility layer for MAT's dense form and for tests: plain torch ops on device tensors, off the hot path - the
+    ragged MAT model never forms the matrix (layers/conv/mat_conv.py).  Edges with an index ``>= n_max`` are dropped, like
+    the reference does."""
+
+    def __init__(self, n_max: int = None, return_mask: bool = True, use_node_tensor: bool = True, **kwargs):
+        super().__init__(**kwargs)
+        self.n_max = int(n_max) if n_max else None
+        self.return_mask = bool(return_mask)
+        self.use_node_tensor = use_node_tensor
+
+    def call(self, inputs, **kwargs):
+        if self.use_node_tensor:
+            nodes, edges, indices = self.assert_ragged_input_rank(inputs, ragged_rank=1)
+        else:
+            edges, indices = self.assert_ragged_input_rank(inputs, ragged_rank=1)
+            nodes = None
+        idx, vals, batch = indices.values, edges.values, indices.value_rowids()
+        if self.n_max:
+            n_max = self.n_max
+            keep = (idx < n_max).all(dim=-1)
+            idx, vals, batch = idx[keep], vals[keep], batch[keep]
+        elif nodes is not None:
+            n_max = int(nodes.row_lengths().max()) if nodes.nrows() > 0 else 0
+        else:
+            n_max = int(idx.max()) + 1 if idx.numel() > 0 else 0
+        g = indices.nrows()
+        flat = (batch * n_max + idx[:, 0]) * n_max + idx[:, 1]
+        adj = torch.zeros((g * n_max * n_max,) + tuple(vals.shape[1:]), dtype=vals.dtype, device=vals.device)
+        adj.index_add_(0, flat, vals)
+        adj = adj.view((g, n_max, n_max) + tuple(vals.shape[1:]))
+        mask = None
+        if self.return_mask:
+            mask = torch.zeros(g * n_max * n_max, dtype=vals.dtype, device=vals.device)
+            mask.index_add_(0, flat, torch.ones(flat.shape[0], dtype=vals.dtype, device=vals.device))
+            mask = mask.view(g, n_max, n_max)
+        return adj, mask
+
+    def get_config(self):
+        config = super().get_config()
+        config.update({"n_max": self.n_max, "return_mask": self.return_mask, "use_node_tensor": self.use_node_tensor})
+        return config

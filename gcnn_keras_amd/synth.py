@@ -794,3 +794,39 @@ def megan_params(model, seed=53, dense_scale=1.0):
     biases in +-0.1, embeddings in +-0.5.  At scale 1 the summed attention logits stay of order 1, so the edge
     importances do not saturate."""
     return relational_params(model, seed=seed, dense_scale=dense_scale)
+
+
+def mat_batch(num_graphs=128, seed=9012, sigma=1.6, min_distance=0.9, **kwargs):
+    """MAT inputs on the :func:`cmpnn_batch` bond graphs (``kwargs`` go there): additionally ``node_coordinates``
+    ``(N, 3)`` float32 from :func:`_molecule` (Angstrom, ``min_distance`` apart) and ``edge_weights`` ``(M, 1)`` float32,
+    a bond order in {1, 1.5, 2, 3} equal for both directions of a bond; ``node_number`` is float32 for the embedding
+    input."""
+    b = cmpnn_batch(num_graphs, seed=seed, **kwargs)
+    rng = np.random.default_rng(seed + 3)
+    ns, es = b["node_splits"], b["edge_splits"]
+    b["node_coordinates"] = np.concatenate(
+        [_molecule(rng, int(ns[g + 1] - ns[g]), sigma, min_distance) for g in range(num_graphs)]
+        + [np.zeros((0, 3))], axis=0).astype(np.float32)
+    orders = np.array([1.0, 1.5, 2.0, 3.0], dtype=np.float32)
+    weights = np.zeros((int(es[-1]), 1), dtype=np.float32)
+    for g in range(num_graphs):
+        lo, hi = int(es[g]), int(es[g + 1])
+        idx, rev = b["edge_indices"][lo:hi], b["edge_indices_reverse"][lo:hi, 0]
+        draw = orders[rng.integers(0, 4, size=hi - lo)]
+        weights[lo:hi, 0] = np.where(idx[:, 0] < idx[:, 1], draw, draw[rev])
+    b["edge_weights"] = weights
+    b["node_number"] = b["node_number"].astype(np.float32)
+    return b
+
+
+def mat_params(model, seed=59, dense_scale=0.5):
+    """Random weights for a built MAT ``model`` in ``model.weights`` order (``cmpnn_params``' rules: Dense kernels
+    Glorot-uniform times ``dense_scale``, biases in +-0.1, embeddings in +-0.5); the layer normalisations' ``gamma`` in
+    ``1 +- 0.1`` and ``beta`` in ``+-0.1``, so that neither is the identity."""
+    rng = np.random.default_rng(seed)
+    p = cmpnn_params(model, seed=seed, dense_scale=dense_scale)
+    for key in p:
+        leaf = key.rsplit("/", 1)[-1]
+        if leaf in ("gamma", "beta"):
+            p[key] = ((1.0 if leaf == "gamma" else 0.0) + rng.uniform(-0.1, 0.1, size=p[key].shape)).astype(np.float32)
+    return p
