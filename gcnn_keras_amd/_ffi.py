@@ -34,6 +34,7 @@ MP_MAT_RECV_TILE, MP_MAT_SEND_TILE = 16, 64
 MP_MAT_TRAFO_NONE, MP_MAT_TRAFO_EXP, MP_MAT_TRAFO_SOFTMAX = 0, 1, 2
 MP_MAT_MERGE_CONCAT, MP_MAT_MERGE_SUM = 0, 1
 MP_MAT_EPILOGUE_MAX_CHANNELS, MP_MAT_EPILOGUE_MAX_WIDTH = 256, 256
+MP_TOPK_ACC_FLOATS = 2048   # include/mpengine.h: row accumulator of the adjacency product, per wave
 
 ACTIVATION_CODES = {
     None: 0, "linear": 0, "relu": 1, "kgcnn>shifted_softplus": 2, "shifted_softplus": 2, "softplus": 3,
@@ -248,6 +249,18 @@ _SIGNATURES = {
     # MAT (csrc/mp_mat.hip): all-pairs molecule attention on ragged rows, optional merge + residual epilogue
     "mp_mat_attention_f32": [P, c_int64, P, c_int64, P, c_int64, c_int64, c_int, c_int, P, P, c_int64, P, P, P, P, c_int64,
                              c_int, c_float, c_float, c_float, c_int, P, c_int64, c_int, P, P, P, P],
+    # hierarchical pooling (csrc/mp_topk.hip): top-k selection, induced edges, A . B on edge lists, unpool
+    "mp_topk_workspace_bytes": [c_int64, P],
+    "mp_topk_select_f32": [P, c_int64, c_int64, P, P, c_int64, c_float, c_int64, c_int, P, P, P, P, P, P, P, c_size_t, P],
+    "mp_topk_edges_count_i32": [P, P, P, c_int64, c_int64, P, P, c_int64, P, c_int64, P, P, P, c_size_t, P],
+    "mp_topk_edges_fill_f32": [P, P, P, c_int64, c_int64, P, P, c_int64, P, P, c_int64, P, c_int64, P, c_int64, c_int, P,
+                               P, P, P, P, P, P, P],
+    "mp_adjacency_product_count_f32": [P, P, P, P, c_int64, c_int64, P, P, P, P, c_int64, c_int64, c_int64, P, c_int64,
+                                       c_float, c_int, P, P, P, c_size_t, P],
+    "mp_adjacency_product_fill_f32": [P, P, P, P, c_int64, c_int64, P, P, P, P, c_int64, c_int64, c_int64, P, c_int64,
+                                      c_float, c_int, P, c_int64, c_int, P, P, P, P, P],
+    "mp_topk_invert_map_i64": [P, c_int64, P, P, c_int64, c_int, c_int64, P, P],
+    "mp_topk_unpool_f32": [P, c_int64, c_int64, P, c_int64, P, P, P],
     "mp_scaler_species_count": [P, c_int, P, c_int64, c_int64, P, P, P, P, P],
     "mp_scaler_fit_ws_bytes": [c_int64, c_int, P],
     "mp_scaler_normal_f64": [P, P, c_int64, P, c_int, c_int, P, c_double, c_int, P, P, P, P, c_size_t, P],

@@ -830,3 +830,49 @@ def mat_params(model, seed=59, dense_scale=0.5):
         if leaf in ("gamma", "beta"):
             p[key] = ((1.0 if leaf == "gamma" else 0.0) + rng.uniform(-0.1, 0.1, size=p[key].shape)).astype(np.float32)
     return p
+
+
+def unet_batch(num_graphs=128, seed=7, node_features=12, **kwargs):
+    """Graph U-Net inputs on the :func:`cmpnn_batch` bond graphs (``kwargs`` go there): ``node_attributes``
+    ``(N, node_features)`` float32 ``N(0, 1)`` (continuous, so that scores differ unless rows are bit-equal) and
+    ``edge_weights`` ``(M, 1)`` float32 ``0.5 + |0.3 N(0, 1)|`` from a stream of their own (``seed + 4``): positive
+    adjacency weights in column 0, which keep every entry of ``A^2`` far above the Keras epsilon at every level (with the
+    Keras default edge embedding, +-0.05, the entries fall below 1e-7 by the third level and every edge goes).
+    ``node_number`` and ``edge_number`` are float32 for the embedding inputs of the default model.
+
+    The pooled structure is a discontinuous function of the scores and of the threshold, so a comparison against another
+    implementation needs inputs on which near-ties and near-threshold entries do not occur; tests/test_unet_api.py
+    asserts that for ``unet_batch(12)`` with ``unet_params`` (the default seeds were searched for it)."""
+    b = cmpnn_batch(num_graphs, seed=seed, **kwargs)
+    rng = np.random.default_rng(seed + 4)
+    n, m = int(b["node_splits"][-1]), int(b["edge_splits"][-1])
+    b["node_attributes"] = rng.normal(size=(n, node_features)).astype(np.float32)
+    b["edge_weights"] = (0.5 + np.abs(0.3 * rng.normal(size=(m, 1)))).astype(np.float32)
+    b["node_number"] = b["node_number"].astype(np.float32)
+    b["edge_number"] = b["edge_number"].astype(np.float32)
+    return b
+
+
+def unet_params(model, seed=61, dense_scale=1.3):
+    """Random weights for a built Graph U-Net ``model`` in ``model.weights`` order: Dense kernels Glorot-uniform times
+    ``dense_scale``, biases in +-0.1, the pooling scores in ``1 +- 0.2``, a node embedding in +-0.5 and an edge embedding
+    ``0.5 + |0.3 N(0, 1)|`` (positive adjacency weights, see :func:`unet_batch`).  At scale 1.3 the default model's
+    outputs spread over 0.2 .. 0.5; at 2 the nine convolutions drive the output sigmoid into saturation."""
+    rng = np.random.default_rng(seed)
+    p = {}
+    tables = [i for i, (name, _) in enumerate(model.weights) if name.rsplit("/", 1)[-1] == "embeddings"]
+    edge_table = tables[-1] if tables and model.config.get("edge_input_dim") is not None else -1
+    for i, (name, t) in enumerate(model.weights):
+        shape = tuple(int(s) for s in t.shape)
+        leaf = name.rsplit("/", 1)[-1]
+        if leaf == "embeddings":
+            edge = i == edge_table
+            v = 0.5 + np.abs(0.3 * rng.normal(size=shape)) if edge else rng.uniform(-0.5, 0.5, size=shape)
+        elif leaf == "bias":
+            v = rng.uniform(-0.1, 0.1, size=shape)
+        elif leaf == "score":
+            v = 1.0 + rng.uniform(-0.2, 0.2, size=shape)
+        else:
+            v = dense_scale * glorot_uniform(rng, shape[0], shape[-1], shape=shape)
+        p["%03d/%s" % (i, name)] = np.asarray(v, dtype=np.float32)
+    return p
