@@ -108,6 +108,9 @@ _SIGNATURES = {
     "mp_cfconv_fused_ws_f32": [P, c_int64, P, c_int, P, P, P, P, c_int64, c_int, P, P, c_size_t, P],
     "mp_cfconv_gauss_fused_ws_f32": [P, c_int64, P, c_int, c_float, c_float, c_float, P, P, P, P, c_int64, c_int, P, P,
                                      c_size_t, P],
+    "mp_cfconv_filter_table_layout": [c_int, c_float, c_float, c_float, c_int, P],
+    "mp_cfconv_filter_table_f32": [P, P, c_int, P, P, c_float, c_float, c_float, P, P, P, P],
+    "mp_cfconv_table_f32": [P, c_int64, P, c_float, P, P, P, P, P, c_int64, c_int, c_int, P, P, c_size_t, P],
     "mp_cfconv_bwd_packed_floats": [],
     "mp_cfconv_bwd_pack_f32": [P, P, c_int, P, P, P],
     "mp_cfconv_gauss_dist_grad_f32": [P, P, c_int64, P, c_int, c_float, c_float, c_float, P, P, P, c_int64, c_int, P, P],
@@ -274,6 +277,15 @@ MP_SCHNET_MAX_DEPTH = 8
 MP_SCHNET_TABLE_MAX_ROWS = 2048   # include/mpengine.h: rows of the node-input tables (vocab + 1)
 
 
+MP_FILTER_TABLE_MAX_ROWS = 256    # include/mpengine.h: rows of a cfconv filter table
+
+
+class FilterTableLayout(ctypes.Structure):
+    """``mp_filter_table_layout`` of include/mpengine.h."""
+    _fields_ = [("v_lo", c_float), ("v_end", c_float), ("inv_h", c_float), ("n_int", ctypes.c_int32),
+                ("rows", ctypes.c_int32)]
+
+
 class SchnetForwardDesc(ctypes.Structure):
     """``mp_schnet_forward_desc`` of include/mpengine.h (field for field)."""
     _fields_ = ([("N", c_int64), ("M", c_int64), ("G", c_int64),
@@ -285,7 +297,8 @@ class SchnetForwardDesc(ctypes.Structure):
                 + [(name, c_void_p * MP_SCHNET_MAX_DEPTH) for name in ("Wx", "packed", "W2", "b2", "W3", "b3")]
                 + [(name, c_void_p) for name in ("Wl0", "bl0", "Wl1", "bl1", "Wo0", "bo0", "Wo1", "bo1", "recv", "send",
                                                  "dist", "flags_word", "n", "x", "agg", "h", "out",
-                                                 "n_table", "x_table")])
+                                                 "n_table", "x_table")]
+                + [("filter_table", c_void_p * MP_SCHNET_MAX_DEPTH), ("filter_layout", FilterTableLayout)])
 
 
 class SchnetForceDesc(ctypes.Structure):

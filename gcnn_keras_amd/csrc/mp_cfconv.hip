@@ -47,6 +47,11 @@
 //    matrix work are written for instruction count (packed FP32, scalar control, 6-instruction softplus).
 //  * The output buffer must be zero on entry (unconnected nodes keep 0 = the has_unconnected pad of
 //    kgcnn/layers/pooling.py:74-76).
+//
+// The inference forward does not run this kernel when it can avoid it: the filter is a function of the distance alone,
+// so cfconv_table_kernel (end of this file) interpolates it from a per-block table rebuilt at every
+// weight update and shares the segment walk below; the MFMA kernel serves the layer API, the force pass, training and
+// the blocks whose table misses its self-check.
 #include <type_traits>
 
 #include "mp_common.h"
@@ -108,6 +113,105 @@ struct CfconvArgs {
   int32_t* bnd_node;
   unsigned long long* diag;  // optional [8] cycle sums per phase (diagnostic build only)
 };
+
+// ---- the segment walk of one 32-edge tile, shared by the MFMA kernel and the table kernel (cfconv_table_kernel):
+//      `msg(r, m01, m23)` yields the messages of edge step r (edges r and 16 + r of the tile, the lane's four features
+//      as two register pairs), `stamp(i)` is the diagnostic build's cycle stamp. ----
+// the tile's 32-bit segment-start mask: bit e = edge e has another receiver than edge e - 1 (my_recv in plain edge order)
+__device__ __forceinline__ unsigned cfconv_segment_mask(int my_recv, int c) {
+  const int prev_recv = __shfl_up(my_recv, 1, 64);  // all lanes take part; lanes 0 / 32 are masked out below
+  return static_cast<unsigned>(__ballot((c > 0) & (my_recv != prev_recv)) & 0xffffffffull);
+}
+template <class Msg, class Stamp>
+__device__ __forceinline__ void cfconv_segment_walk(const CfconvArgs& a, int tile, int my_recv, unsigned sm, int c, int hh,
+                                                    float* xs_half, Msg msg, Stamp stamp) {
+  constexpr unsigned long long LO = 0x00000000ffffffffull, HI = 0xffffffff00000000ull;
+  float* const out_lane = a.out + 4 * c;
+  floatx2 acc01, acc23;
+  msg(0, acc01, acc23);
+  floatx2 first01 = {0.0f, 0.0f}, first23 = {0.0f, 0.0f};
+  unsigned had = 0;  // scalar: bit 0 / 1 = a segment has opened inside the low / high half
+#pragma unroll
+  for (int r = 1; r < 16; ++r) {
+    const unsigned o = (sm >> r) & 0x10001u;  // bit 0: edge r opens a segment; bit 16: edge 16 + r does
+    floatx2 m01, m23;
+    msg(r, m01, m23);
+    if (o != 0) {
+      const bool o_lo = (o & 1u) != 0, o_hi = (o >> 16) != 0;
+      const unsigned long long open_mask = (o_lo ? LO : 0ull) | (o_hi ? HI : 0ull);
+      const unsigned long long store_mask = ((o_lo && (had & 1u)) ? LO : 0ull) | ((o_hi && (had & 2u)) ? HI : 0ull);
+      if (__builtin_amdgcn_inverse_ballot_w64(store_mask)) {
+        const int row_lo = __builtin_amdgcn_readlane(my_recv, r - 1);
+        const int row_hi = __builtin_amdgcn_readlane(my_recv, 16 + r - 1);
+        *reinterpret_cast<float4*>(out_lane + static_cast<int64_t>(hh ? row_hi : row_lo) * F) =
+            make_float4(acc01.x, acc01.y, acc23.x, acc23.y);
+      }
+      if (__builtin_amdgcn_inverse_ballot_w64(open_mask & ~store_mask)) {  // the half's first segment closes: keep it
+        first01 = acc01;
+        first23 = acc23;
+      }
+      if (__builtin_amdgcn_inverse_ballot_w64(open_mask)) {  // restart (the add below then yields m)
+        acc01 = floatx2{0.0f, 0.0f};
+        acc23 = floatx2{0.0f, 0.0f};
+      }
+      had |= (o_lo ? 1u : 0u) | (o_hi ? 2u : 0u);
+    }
+    acc01 += m01;
+    acc23 += m23;
+  }
+  float acc[4] = {acc01.x, acc01.y, acc23.x, acc23.y};
+  float first[4] = {first01.x, first01.y, first23.x, first23.y};
+  stamp(5);
+  // wave-uniform shape of the tile
+  const int nlo = __builtin_popcount(sm & 0xfffeu) + 1;   // segments touching the low half
+  const int nhi = __builtin_popcount(sm >> 17) + 1;        // segments touching the high half
+  const bool cont = ((sm >> 16) & 1u) == 0;                // edge 16 continues the segment of edge 15
+  const int node_e0 = __builtin_amdgcn_readlane(my_recv, 0), node_e15 = __builtin_amdgcn_readlane(my_recv, 15);
+  const int node_e16 = __builtin_amdgcn_readlane(my_recv, 16), node_e31 = __builtin_amdgcn_readlane(my_recv, 31);
+  // Float atomics leave the XCD (device scope) and are paid per 128-B line touched: the lane's four features
+  // 4c..4c+3 are first transposed through 512 B of LDS so that each of the four atomic instructions of a half wave
+  // covers ONE contiguous line (features 32 jb + c) instead of four (measured: 3.3 us -> <1 us per launch at config 2).
+  auto atomic_row = [&](int node, int which, float v0, float v1, float v2, float v3) {
+    if (a.bnd_val != nullptr) {  // deterministic mode: park the partial row, slot `which` (0 = tile's first segment)
+      const int64_t slot = 2 * static_cast<int64_t>(tile) + which;
+      *reinterpret_cast<float4*>(a.bnd_val + slot * F + 4 * c) = make_float4(v0, v1, v2, v3);
+      if (c == 0) a.bnd_node[slot] = node;
+      return;
+    }
+    *reinterpret_cast<float4*>(xs_half + 4 * c) = make_float4(v0, v1, v2, v3);
+    float* dst = a.out + static_cast<int64_t>(node) * F + c;
+#pragma unroll
+    for (int jb = 0; jb < 4; ++jb) atomicAdd(dst + jb * 32, xs_half[jb * 32 + c]);
+  };
+  auto store_row = [&](int node, float v0, float v1, float v2, float v3) {
+    *reinterpret_cast<float4*>(out_lane + static_cast<int64_t>(node) * F) = make_float4(v0, v1, v2, v3);
+  };
+  float tail[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  if (cont) {  // hand the low half's open tail to the high half (lanes c + 32)
+#pragma unroll
+    for (int jb = 0; jb < 4; ++jb) tail[jb] = __shfl_xor(acc[jb], 32, 64);
+  }
+  stamp(6);
+  if (hh == 0) {
+    if (nlo > 1) atomic_row(node_e0, 0, first[0], first[1], first[2], first[3]);  // first segment closed in the low half
+    if (!cont) {    // the low half's last segment ends at edge 15
+      if (nlo == 1) atomic_row(node_e15, 0, acc[0], acc[1], acc[2], acc[3]);      // it is also the tile's first
+      else store_row(node_e15, acc[0], acc[1], acc[2], acc[3]);
+    }
+  } else {
+    // the high half's first segment (the whole half if nhi == 1), plus the low half's tail when it continues
+    float v0[4];
+#pragma unroll
+    for (int jb = 0; jb < 4; ++jb) {
+      const float mine = nhi > 1 ? first[jb] : acc[jb];
+      v0[jb] = cont ? tail[jb] + mine : mine;   // edge order: low-half part first
+    }
+    // tile's first segment (it reaches back to edge 0) or its last one (it reaches edge 31) - or the whole tile
+    if ((cont && nlo == 1) || nhi == 1) atomic_row(node_e16, (cont && nlo == 1) ? 0 : 1, v0[0], v0[1], v0[2], v0[3]);
+    else store_row(node_e16, v0[0], v0[1], v0[2], v0[3]);
+    if (nhi > 1) atomic_row(node_e31, 1, acc[0], acc[1], acc[2], acc[3]);                  // the tile's last segment
+  }
+}
 
 #define MP_STAMP(idx)                                                                  \
   if constexpr (DIAG) {                                                                \
@@ -652,10 +756,7 @@ __global__ __launch_bounds__(WAVES * 64, 1) void cfconv_fused_kernel(CfconvArgs 
     //      segment continues across edge 15|16; tile-interior ones are stored, the tile's first and last segment -
     //      which may continue in the neighbouring tiles - are added with float atomics.  Padding edges of the last
     //      tile repeat the last receiver and carry zeros. -----------------------------------------------------------------
-    const int prev_recv = __shfl_up(my_recv, 1, 64);  // all lanes take part; lanes 0 / 32 are masked out below
-    const unsigned sm = static_cast<unsigned>(__ballot((c > 0) & (my_recv != prev_recv)) & 0xffffffffull);
-    constexpr unsigned long long LO = 0x00000000ffffffffull, HI = 0xffffffff00000000ull;
-    float* const out_lane = a.out + 4 * c;
+    const unsigned sm = cfconv_segment_mask(my_recv, c);
     if (e0 + TE > a.M) {  // the one partial tile: its padding edges carry zeros
       const int rows_valid = static_cast<int>(a.M - e0) - 16 * hh;
 #pragma unroll
@@ -665,91 +766,13 @@ __global__ __launch_bounds__(WAVES * 64, 1) void cfconv_fused_kernel(CfconvArgs 
     }
     // features (4c, 4c+1) and (4c+2, 4c+3) as register pairs: v_pk_mul_f32 / v_pk_add_f32 do two columns per instruction
     const floatx2 b01 = {bias2[0], bias2[1]}, b23 = {bias2[2], bias2[3]};   // filter = h W2 + b2, as Dense adds it
-    floatx2 acc01 = (floatx2{w[0][0], w[1][0]} + b01) * floatx2{xv[0][0], xv[1][0]};
-    floatx2 acc23 = (floatx2{w[2][0], w[3][0]} + b23) * floatx2{xv[2][0], xv[3][0]};
-    floatx2 first01 = {0.0f, 0.0f}, first23 = {0.0f, 0.0f};
-    unsigned had = 0;  // scalar: bit 0 / 1 = a segment has opened inside the low / high half
-#pragma unroll
-    for (int r = 1; r < 16; ++r) {
-      const unsigned o = (sm >> r) & 0x10001u;  // bit 0: edge r opens a segment; bit 16: edge 16 + r does
-      const floatx2 m01 = (floatx2{w[0][r], w[1][r]} + b01) * floatx2{xv[0][r], xv[1][r]};
-      const floatx2 m23 = (floatx2{w[2][r], w[3][r]} + b23) * floatx2{xv[2][r], xv[3][r]};
-      if (o != 0) {
-        const bool o_lo = (o & 1u) != 0, o_hi = (o >> 16) != 0;
-        const unsigned long long open_mask = (o_lo ? LO : 0ull) | (o_hi ? HI : 0ull);
-        const unsigned long long store_mask = ((o_lo && (had & 1u)) ? LO : 0ull) | ((o_hi && (had & 2u)) ? HI : 0ull);
-        if (__builtin_amdgcn_inverse_ballot_w64(store_mask)) {
-          const int row_lo = __builtin_amdgcn_readlane(my_recv, r - 1);
-          const int row_hi = __builtin_amdgcn_readlane(my_recv, 16 + r - 1);
-          *reinterpret_cast<float4*>(out_lane + static_cast<int64_t>(hh ? row_hi : row_lo) * F) =
-              make_float4(acc01.x, acc01.y, acc23.x, acc23.y);
-        }
-        if (__builtin_amdgcn_inverse_ballot_w64(open_mask & ~store_mask)) {  // the half's first segment closes: keep it
-          first01 = acc01;
-          first23 = acc23;
-        }
-        if (__builtin_amdgcn_inverse_ballot_w64(open_mask)) {  // restart (the add below then yields m)
-          acc01 = floatx2{0.0f, 0.0f};
-          acc23 = floatx2{0.0f, 0.0f};
-        }
-        had |= (o_lo ? 1u : 0u) | (o_hi ? 2u : 0u);
-      }
-      acc01 += m01;
-      acc23 += m23;
-    }
-    float acc[4] = {acc01.x, acc01.y, acc23.x, acc23.y};
-    float first[4] = {first01.x, first01.y, first23.x, first23.y};
-    MP_STAMP(5)
-    // wave-uniform shape of the tile
-    const int nlo = __builtin_popcount(sm & 0xfffeu) + 1;   // segments touching the low half
-    const int nhi = __builtin_popcount(sm >> 17) + 1;        // segments touching the high half
-    const bool cont = ((sm >> 16) & 1u) == 0;                // edge 16 continues the segment of edge 15
-    const int node_e0 = __builtin_amdgcn_readlane(my_recv, 0), node_e15 = __builtin_amdgcn_readlane(my_recv, 15);
-    const int node_e16 = __builtin_amdgcn_readlane(my_recv, 16), node_e31 = __builtin_amdgcn_readlane(my_recv, 31);
-    // Float atomics leave the XCD (device scope) and are paid per 128-B line touched: the lane's four features
-    // 4c..4c+3 are first transposed through 512 B of LDS so that each of the four atomic instructions of a half wave
-    // covers ONE contiguous line (features 32 jb + c) instead of four (measured: 3.3 us -> <1 us per launch at config 2).
-    float* const xs_half = Xs + (wave * 2 + hh) * F;
-    auto atomic_row = [&](int node, int which, float v0, float v1, float v2, float v3) {
-      if (a.bnd_val != nullptr) {  // deterministic mode: park the partial row, slot `which` (0 = tile's first segment)
-        const int64_t slot = 2 * static_cast<int64_t>(tile) + which;
-        *reinterpret_cast<float4*>(a.bnd_val + slot * F + 4 * c) = make_float4(v0, v1, v2, v3);
-        if (c == 0) a.bnd_node[slot] = node;
-        return;
-      }
-      *reinterpret_cast<float4*>(xs_half + 4 * c) = make_float4(v0, v1, v2, v3);
-      float* dst = a.out + static_cast<int64_t>(node) * F + c;
-#pragma unroll
-      for (int jb = 0; jb < 4; ++jb) atomicAdd(dst + jb * 32, xs_half[jb * 32 + c]);
-    };
-    auto store_row = [&](int node, float v0, float v1, float v2, float v3) {
-      *reinterpret_cast<float4*>(out_lane + static_cast<int64_t>(node) * F) = make_float4(v0, v1, v2, v3);
-    };
-    float tail[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (cont) {  // hand the low half's open tail to the high half (lanes c + 32)
-#pragma unroll
-      for (int jb = 0; jb < 4; ++jb) tail[jb] = __shfl_xor(acc[jb], 32, 64);
-    }
-    MP_STAMP(6)
-    if (hh == 0) {
-      if (nlo > 1) atomic_row(node_e0, 0, first[0], first[1], first[2], first[3]);  // first segment closed in the low half
-      if (!cont) {    // the low half's last segment ends at edge 15
-        if (nlo == 1) atomic_row(node_e15, 0, acc[0], acc[1], acc[2], acc[3]);      // it is also the tile's first
-        else store_row(node_e15, acc[0], acc[1], acc[2], acc[3]);
-      }
-    } else {
-      // the high half's first segment (the whole half if nhi == 1), plus the low half's tail when it continues
-      float v0[4];
-#pragma unroll
-      for (int jb = 0; jb < 4; ++jb) {
-        const float mine = nhi > 1 ? first[jb] : acc[jb];
-        v0[jb] = cont ? tail[jb] + mine : mine;   // edge order: low-half part first
-      }
-      // tile's first segment (it reaches back to edge 0) or its last one (it reaches edge 31) - or the whole tile
-      if ((cont && nlo == 1) || nhi == 1) atomic_row(node_e16, (cont && nlo == 1) ? 0 : 1, v0[0], v0[1], v0[2], v0[3]);
-      else store_row(node_e16, v0[0], v0[1], v0[2], v0[3]);
-      if (nhi > 1) atomic_row(node_e31, 1, acc[0], acc[1], acc[2], acc[3]);                  // the tile's last segment
-    }
+    cfconv_segment_walk(
+        a, tile, my_recv, sm, c, hh, Xs + (wave * 2 + hh) * F,
+        [&](int r, floatx2& m01, floatx2& m23) {
+          m01 = (floatx2{w[0][r], w[1][r]} + b01) * floatx2{xv[0][r], xv[1][r]};
+          m23 = (floatx2{w[2][r], w[3][r]} + b23) * floatx2{xv[2][r], xv[3][r]};
+        },
+        [&](int idx) { MP_STAMP(idx) });
     MP_STAMP(7)
   }
   // a wave without tiles still owes the workgroup its barrier (and must not exit under its DMA)
@@ -966,6 +989,276 @@ CfconvArgs make_args(const float* x, int64_t N, const float* edge_in, int B, con
   return a;
 }
 
+// ================================================================================================ filter table
+// The filter of an edge, w(d) = Dense(F, linear)(Dense(F, ssp)(gauss(d))), depends on the block's weights and on ONE
+// scalar.  For the inference forward it is tabulated once per weight update: row j of the table is the filter at the knot
+// v_j = v_lo + (j - 2) h of v = d - offset (evaluated in double precision, rounded to FP32 once, b2 included, features in
+// natural order: lane c reads 4c..4c+3 with one ds_read_b128), and the kernel interpolates with six-point Lagrange
+// weights on the knots i-2 .. i+3 of the interval i that holds v.  h is a power of two, so t = (v - v_lo) / h and
+// u = t - i are exact.  Beyond the ends of the domain every Gaussian is below 2.3e-11: v is clamped.  DESIGN.md 3.28.
+using FtLayout = mp_filter_table_layout;
+
+struct FtPoint {
+  float w[6];   // Lagrange weights of the rows i .. i + 5
+  int i;        // interval = first row
+};
+
+// The interpolation arithmetic - one function for the kernel and for the self-check of the table build.
+__device__ __forceinline__ FtPoint ft_point(float d, float offset, const FtLayout& L) {
+  const float v = fminf(fmaxf(d - offset, L.v_lo), L.v_end);
+  const float t = (v - L.v_lo) * L.inv_h;
+  int i = static_cast<int>(t);
+  i = i < 0 ? 0 : (i > L.n_int - 1 ? L.n_int - 1 : i);
+  const float u = t - static_cast<float>(i);
+  // nodes -2 .. 3: w_k = prod_{m != k} (u - x_m) / (x_k - x_m); the denominators are -120, 24, -12, 12, -24, 120
+  const float f0 = u + 2.0f, f1 = u + 1.0f, f2 = u, f3 = u - 1.0f, f4 = u - 2.0f, f5 = u - 3.0f;
+  const float A = f0 * f1, B = f2 * f3, C = f4 * f5;
+  const float BC = B * C, AC = A * C, AB = A * B;
+  FtPoint p;
+  p.w[0] = (f1 * BC) * (-1.0f / 120.0f);
+  p.w[1] = (f0 * BC) * (1.0f / 24.0f);
+  p.w[2] = (f3 * AC) * (-1.0f / 12.0f);
+  p.w[3] = (f2 * AC) * (1.0f / 12.0f);
+  p.w[4] = (f5 * AB) * (-1.0f / 24.0f);
+  p.w[5] = (f4 * AB) * (1.0f / 120.0f);
+  p.i = i;
+  return p;
+}
+// the accumulation over the six rows, fixed order k = 0 .. 5: one product, five fused multiply-adds
+__device__ __forceinline__ floatx2 ft_accumulate(const float (&w)[6], const floatx2 (&r)[6]) {
+  floatx2 acc = floatx2{w[0], w[0]} * r[0];
+#pragma unroll
+  for (int k = 1; k < 6; ++k) acc = __builtin_elementwise_fma(floatx2{w[k], w[k]}, r[k], acc);
+  return acc;
+}
+
+// the filter in double precision at v = d - offset: feature f = threadIdx.x of a 128-thread block (hs: 128 doubles of LDS)
+__device__ double ft_filter_f64(double v, const float* W1, const float* b1, int B, const float* W2, const float* b2,
+                                double distance, double gamma, double* hs) {
+  const int f = threadIdx.x;
+  double acc = b1 ? static_cast<double>(b1[f]) : 0.0;
+  for (int k = 0; k < B; ++k) {
+    const double mu = static_cast<double>(k) / static_cast<double>(B) * distance;   // geom.py:567-571
+    acc += exp(-gamma * (v - mu) * (v - mu)) * static_cast<double>(W1[k * F + f]);
+  }
+  __syncthreads();   // the previous point's readers are done with hs
+  hs[f] = fmax(acc, 0.0) + log1p(exp(-fabs(acc))) - 0.6931471805599453094;   // shifted softplus, kgcnn/ops/activ.py:15
+  __syncthreads();
+  double o = b2 ? static_cast<double>(b2[f]) : 0.0;
+  for (int j = 0; j < F; ++j) o += hs[j] * static_cast<double>(W2[j * F + f]);
+  return o;
+}
+
+__global__ __launch_bounds__(F) void cfconv_filter_table_kernel(const float* __restrict__ W1, const float* __restrict__ b1,
+                                                               int B, const float* __restrict__ W2,
+                                                               const float* __restrict__ b2, double distance, double gamma,
+                                                               FtLayout L, float* __restrict__ table) {
+  __shared__ double hs[F];
+  const int j = blockIdx.x;
+  float val = 0.0f;   // (padding rows up to the even row count: never read)
+  if (j < L.n_int + 5) {   // block-uniform
+    const double v = static_cast<double>(L.v_lo) + static_cast<double>(j - 2) / static_cast<double>(L.inv_h);
+    val = static_cast<float>(ft_filter_f64(v, W1, b1, B, W2, b2, distance, gamma, hs));
+  }
+  table[static_cast<int64_t>(j) * F + threadIdx.x] = val;
+}
+
+// Self-check: check point q of interval i = q / 3 lies at u = (q % 3 + 1) / 4; the last four points lie beyond the ends
+// (v_lo - 1 but no distance below 0, v_end + 1/64, v_end + 4, v_end + 1000).  check[0] = max |interpolant - filter|, check[1] = max |filter|
+// (bit patterns of non-negative floats order like unsigned integers).
+__global__ __launch_bounds__(F) void cfconv_filter_check_kernel(const float* __restrict__ W1, const float* __restrict__ b1,
+                                                               int B, const float* __restrict__ W2,
+                                                               const float* __restrict__ b2, double distance, double gamma,
+                                                               float offset, FtLayout L, const float* __restrict__ table,
+                                                               unsigned* __restrict__ check) {
+  __shared__ double hs[F];
+  __shared__ float red[2][F];
+  const int q = blockIdx.x, f = threadIdx.x;
+  const float h = 1.0f / L.inv_h;
+  float v;
+  if (q < 3 * L.n_int) v = L.v_lo + (static_cast<float>(q / 3) + 0.25f * static_cast<float>(q % 3 + 1)) * h;
+  else {
+    const int e = q - 3 * L.n_int;
+    v = e == 0 ? fmaxf(L.v_lo - 1.0f, -offset) : L.v_end + (e == 1 ? 0.015625f : (e == 2 ? 4.0f : 1000.0f));
+  }
+  const float d = v + offset;
+  const FtPoint p = ft_point(d, offset, L);
+  const float* row = table + static_cast<int64_t>(p.i) * F + f;
+  floatx2 r[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) r[k] = floatx2{row[k * F], 0.0f};
+  const float got = ft_accumulate(p.w, r).x;
+  const double ref = ft_filter_f64(static_cast<double>(d - offset), W1, b1, B, W2, b2, distance, gamma, hs);
+  red[0][f] = static_cast<float>(fabs(static_cast<double>(got) - ref));
+  red[1][f] = static_cast<float>(fabs(ref));
+  __syncthreads();
+  for (int s = F / 2; s > 0; s >>= 1) {
+    if (f < s) {
+      red[0][f] = fmaxf(red[0][f], red[0][f + s]);
+      red[1][f] = fmaxf(red[1][f], red[1][f + s]);
+    }
+    __syncthreads();
+  }
+  if (f < 2) atomicMax(check + f, __float_as_uint(red[f][0]));
+}
+
+constexpr int FT_MAX_ROWS = MP_FILTER_TABLE_MAX_ROWS;
+
+// The table kernel: today's tile geometry (32 consecutive edges of the receiver-sorted list per wave, lane half hh holds
+// edges 16 hh .. 16 hh + 15 in step order, lane c the features 4c .. 4c+3), edge data one tile ahead, XCD-aware block
+// order, sender rows requested at tile start - and cfconv_segment_walk, whose message of step r is interpolated on the
+// spot: the lane that owns an edge has written {w0 .. w5, byte offset of row i} to a per-wave LDS scratch (32 B per
+// edge); step r reads its half's entry with two broadcast ds_read_b128, six table rows at immediate offsets k * 512
+// from one address, accumulates in fixed order and multiplies by the sender row.  No MFMA, no transcendental.
+template <int WAVES>
+__global__ __launch_bounds__(WAVES * 64, 1) void cfconv_table_kernel(CfconvArgs a, FtLayout L) {
+  extern __shared__ __align__(16) float lds[];
+  float* Ts = lds;                               // [rows][F] the table
+  float* Es = Ts + L.rows * F;                   // [WAVES][TE][8] per-edge weights and row offset
+  float* Xs = Es + WAVES * TE * 8;               // [WAVES][2][F] lane-transposition scratch for the boundary atomics
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int c = lane & 31;
+  const int hh = lane >> 5;
+
+  const int tile_first = static_cast<int>(mp_xcd_block(blockIdx.x, gridDim.x)) * WAVES + wave;
+  const int tile_step = gridDim.x * WAVES;
+  int nx_send = 0, nx_recv = 0;
+  float nx_d = 0.0f;
+  const int eps_c = 16 * ((c >> 2) & 1) + (c & 3) + 4 * (c >> 3);   // the MFMA kernel's edge of lane c (sender shuffle)
+  auto prefetch_tile = [&](int t) {
+    if (t < a.ntiles) {
+      const int64_t e0n = static_cast<int64_t>(t) * TE;
+      const int64_t e = e0n + eps_c;
+      const int64_t ec = e < a.M ? e : a.M - 1;    // padding edges repeat the last valid one (and carry zeros below)
+      const int64_t ep = a.perm ? static_cast<int64_t>(a.perm[ec]) : ec;
+      nx_send = a.send[ep];
+      const int64_t es = (e0n + c) < a.M ? (e0n + c) : a.M - 1;
+      nx_recv = a.recv[es];
+      nx_d = a.edge_in[ep];
+    }
+  };
+  prefetch_tile(tile_first);
+  // the table by LDS-DMA in 1-KB chunks (two rows), round robin over the waves
+  {
+    const int nchunks = L.rows >> 1;
+    for (int chunk = wave; chunk < nchunks; chunk += WAVES)
+      __builtin_amdgcn_global_load_lds(a.packed + chunk * 256 + lane * 4,
+                                       (__attribute__((address_space(3))) void*)(Ts + chunk * 256), 16, 0, 0);
+  }
+  bool t_ready = false;   // wave-uniform: every wave passes the publishing barrier exactly once
+  float* const es_wave = Es + wave * (TE * 8);
+  const char* const ts_lane = reinterpret_cast<const char*>(Ts) + 16 * c;
+
+  for (int tile0 = tile_first; tile0 < a.ntiles; tile0 += tile_step) {
+    const int tile = __builtin_amdgcn_readfirstlane(tile0);
+    const int64_t e0 = static_cast<int64_t>(tile) * TE;
+    const int my_send = nx_send;
+    const int my_recv = nx_recv;
+    const float d_mine = nx_d;
+    // sender rows: XW of the 16 steps' rows in flight (all of them where the register budget allows: the 16-wave build
+    // has 128 registers per lane and keeps eight, step r re-filling its slot with the row of step r + 8)
+    constexpr int XW = WAVES > 8 ? 8 : 16;
+    floatx2 x01[XW], x23[XW];
+    auto load_sender_row = [&](int r) {
+      const int snode = __shfl(my_send, rowmap(r, hh), 64);   // lane rowmap(r, hh) holds edge 16 hh + r
+      // always in range: padding rows reuse the last valid edge's sender
+      const float4 t = *reinterpret_cast<const float4*>(a.x + static_cast<int64_t>(snode) * F + 4 * c);
+      x01[r % XW] = floatx2{t.x, t.y};
+      x23[r % XW] = floatx2{t.z, t.w};
+    };
+#pragma unroll
+    for (int r = 0; r < XW; ++r) load_sender_row(r);
+    prefetch_tile(tile0 + tile_step);
+    const FtPoint p = ft_point(d_mine, a.g_offset, L);
+    if (hh == 0) {
+      float4* const ent = reinterpret_cast<float4*>(es_wave + eps_c * 8);
+      ent[0] = make_float4(p.w[0], p.w[1], p.w[2], p.w[3]);
+      ent[1] = make_float4(p.w[4], p.w[5], __int_as_float(p.i * (F * 4)), 0.0f);
+    }
+    if (!t_ready) {
+      __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): this wave's share of the table has landed
+      __syncthreads();
+      t_ready = true;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();        // the entries are read by other lanes of this wave (LDS runs in order)
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const bool partial = e0 + TE > a.M;   // the one partial tile: its padding edges carry zeros
+    const int rows_valid = static_cast<int>(a.M - e0) - 16 * hh;
+    const float4* const es_half = reinterpret_cast<const float4*>(es_wave + 16 * hh * 8);
+    cfconv_segment_walk(
+        a, tile, my_recv, cfconv_segment_mask(my_recv, c), c, hh, Xs + (wave * 2 + hh) * F,
+        [&](int r, floatx2& m01, floatx2& m23) {
+          const float4 ea = es_half[2 * r], eb = es_half[2 * r + 1];
+          const float w[6] = {ea.x, ea.y, ea.z, ea.w, eb.x, eb.y};
+          const char* const row = ts_lane + __float_as_int(eb.z);
+          floatx2 r01[6], r23[6];
+#pragma unroll
+          for (int k = 0; k < 6; ++k) {
+            const float4 t = *reinterpret_cast<const float4*>(row + k * (F * 4));
+            r01[k] = floatx2{t.x, t.y};
+            r23[k] = floatx2{t.z, t.w};
+          }
+          floatx2 xa = x01[r % XW], xb = x23[r % XW];
+          if (r + XW < 16) load_sender_row(r + XW);
+          if (partial) {
+            xa = r < rows_valid ? xa : floatx2{0.0f, 0.0f};
+            xb = r < rows_valid ? xb : floatx2{0.0f, 0.0f};
+          }
+          m01 = ft_accumulate(w, r01) * xa;
+          m23 = ft_accumulate(w, r23) * xb;
+        },
+        [](int) {});
+    __builtin_amdgcn_wave_barrier();        // the next tile's entries are written behind this tile's reads
+  }
+  if (!t_ready) {   // a wave without tiles still owes the workgroup its barrier (and must not exit under its DMA)
+    __builtin_amdgcn_s_waitcnt(0x0F70);
+    __syncthreads();
+  }
+}
+
+template <int WAVES>
+int launch_cfconv_table(const CfconvArgs& args, const FtLayout& L, int grid, hipStream_t s) {
+  const size_t lds = sizeof(float) * (static_cast<size_t>(L.rows) * F + WAVES * (TE * 8 + 2 * F));
+  static std::mutex mu;
+  static unsigned long long done_mask = 0;
+  const int rc = mp::ensure_dynamic_lds(reinterpret_cast<const void*>(&cfconv_table_kernel<WAVES>), lds, &done_mask, &mu);
+  if (rc != MP_OK) return rc;
+  cfconv_table_kernel<WAVES><<<grid, WAVES * 64, lds, s>>>(args, L);
+  return mp::check_launch("mp_cfconv_table_f32");
+}
+
+bool ft_layout_ok(const FtLayout& L) {
+  return L.n_int >= 1 && L.rows >= L.n_int + 5 && (L.rows & 1) == 0 && L.rows <= FT_MAX_ROWS && L.inv_h > 0.0f &&
+         L.v_end > L.v_lo;
+}
+
+int cfconv_table_dispatch(CfconvArgs args, const FtLayout& L, int flags, int waves, hipStream_t s) {
+  MP_REQUIRE(args.M >= 0 && args.N >= 0, "mp_cfconv_table_f32: bad sizes");
+  MP_REQUIRE(ft_layout_ok(L), "mp_cfconv_table_f32: bad table layout (rows %d, intervals %d)", L.rows, L.n_int);
+  MP_REQUIRE(waves == 0 || waves == 4 || waves == 8 || waves == 16, "mp_cfconv_table_f32: waves must be 0, 4, 8 or 16");
+  if (args.M == 0 || args.N == 0) return MP_OK;
+  MP_REQUIRE(args.x && args.edge_in && args.packed && args.recv && args.send && args.out, "mp_cfconv_table_f32: null pointer");
+  MP_REQUIRE(args.M < (int64_t{1} << 31), "mp_cfconv_table_f32: M must fit int32");
+  args.ntiles = static_cast<int>((args.M + TE - 1) / TE);
+  // One workgroup per CU (the table takes up to 128 KB of LDS), persistent over the tiles; as many waves per workgroup
+  // as it takes to give every wave a tile in one round of 256 workgroups - a small launch spreads over more CUs.
+  if (waves == 0) waves = args.ntiles <= 1024 ? 4 : (args.ntiles <= 2048 ? 8 : 16);
+  int grid = (args.ntiles + waves - 1) / waves;
+  if ((flags & 16) && grid > 1) grid = (grid + 1) / 2;   // "several forwards in flight", as cfconv_dispatch
+  if (grid > 256) grid = 256;
+  if (args.bnd_val != nullptr)
+    MP_HIP(hipMemsetAsync(args.bnd_node, 0xff, sizeof(int32_t) * 2 * static_cast<size_t>(args.ntiles), s));
+  const int rc = waves == 4 ? launch_cfconv_table<4>(args, L, grid, s)
+                            : (waves == 8 ? launch_cfconv_table<8>(args, L, grid, s) : launch_cfconv_table<16>(args, L, grid, s));
+  if (rc != MP_OK || args.bnd_val == nullptr) return rc;
+  const int64_t nslots = 2 * static_cast<int64_t>(args.ntiles);
+  cfconv_boundary_kernel<<<mp::grid_for(nslots * 32), 256, 0, s>>>(args.bnd_val, args.bnd_node, nslots, args.out);
+  return mp::check_launch("mp_cfconv_table_f32 (deterministic boundary pass)");
+}
+
 }  // namespace
 
 extern "C" {
@@ -1020,6 +1313,56 @@ int mp_cfconv_gauss_fused_ws_f32(const float* x, int64_t N, const float* dist, i
   const int rc = attach_det_workspace(&a, flags, ws, ws_bytes, "mp_cfconv_gauss_fused_ws_f32");
   if (rc != MP_OK) return rc;
   return cfconv_dispatch(a, true, flags, mp::as_stream(stream));
+}
+
+int mp_cfconv_filter_table_layout(int bins, float distance, float sigma, float offset, int log2_inv_h,
+                                  mp_filter_table_layout* layout_out_host) {
+  MP_REQUIRE(layout_out_host != nullptr, "mp_cfconv_filter_table_layout: null pointer");
+  MP_REQUIRE(bins >= 1 && bins <= MAX_KROWS - 2 && sigma != 0.0f && log2_inv_h >= 0 && log2_inv_h <= 10,
+             "mp_cfconv_filter_table_layout: bad basis arguments");
+  const double h = 1.0 / static_cast<double>(1 << log2_inv_h), reach = 7.0 * fabs(static_cast<double>(sigma));
+  const float v_lo = static_cast<float>(fmax(-static_cast<double>(offset), -reach));
+  const double v_hi = static_cast<double>(distance) * (bins - 1) / bins + reach;
+  const double n = ceil((v_hi - static_cast<double>(v_lo)) / h);
+  MP_REQUIRE(n >= 1.0 && n + 6.0 <= FT_MAX_ROWS, "mp_cfconv_filter_table_layout: %g intervals do not fit %d rows", n,
+             FT_MAX_ROWS);
+  mp_filter_table_layout L;
+  L.v_lo = v_lo;
+  L.n_int = static_cast<int>(n);
+  L.v_end = static_cast<float>(static_cast<double>(v_lo) + n * h);
+  L.inv_h = static_cast<float>(1 << log2_inv_h);
+  L.rows = (L.n_int + 5 + 1) & ~1;
+  *layout_out_host = L;
+  return MP_OK;
+}
+
+int mp_cfconv_filter_table_f32(const float* W1, const float* b1, int B, const float* W2, const float* b2, float distance,
+                               float sigma, float offset, const mp_filter_table_layout* layout_host, float* table,
+                               float* check2, mpStream_t stream) {
+  MP_REQUIRE(B >= 1 && B <= MAX_KROWS - 2 && sigma != 0.0f, "mp_cfconv_filter_table_f32: bad basis arguments");
+  MP_REQUIRE(W1 && W2 && table && check2 && layout_host, "mp_cfconv_filter_table_f32: null pointer");
+  const FtLayout L = *layout_host;
+  MP_REQUIRE(ft_layout_ok(L), "mp_cfconv_filter_table_f32: bad table layout (rows %d, intervals %d)", L.rows, L.n_int);
+  hipStream_t s = mp::as_stream(stream);
+  const double gamma = 1.0 / static_cast<double>(sigma) / static_cast<double>(sigma) / 2.0;
+  MP_HIP(hipMemsetAsync(check2, 0, 2 * sizeof(float), s));
+  cfconv_filter_table_kernel<<<L.rows, F, 0, s>>>(W1, b1, B, W2, b2, static_cast<double>(distance), gamma, L, table);
+  int rc = mp::check_launch("mp_cfconv_filter_table_f32");
+  if (rc != MP_OK) return rc;
+  cfconv_filter_check_kernel<<<3 * L.n_int + 4, F, 0, s>>>(W1, b1, B, W2, b2, static_cast<double>(distance), gamma, offset,
+                                                         L, table, reinterpret_cast<unsigned*>(check2));
+  return mp::check_launch("mp_cfconv_filter_table_f32 (self-check)");
+}
+
+int mp_cfconv_table_f32(const float* x, int64_t N, const float* dist, float offset, const float* table,
+                        const mp_filter_table_layout* layout_host, const int32_t* recv_sorted, const int32_t* send,
+                        const int32_t* perm, int64_t M, int flags, int waves, float* out_zeroed, void* ws, size_t ws_bytes,
+                        mpStream_t stream) {
+  MP_REQUIRE(layout_host != nullptr, "mp_cfconv_table_f32: null layout");
+  CfconvArgs a = make_args(x, N, dist, 1, table, recv_sorted, send, perm, M, out_zeroed, 0.0f, 0.0f, offset);
+  const int rc = attach_det_workspace(&a, flags, ws, ws_bytes, "mp_cfconv_table_f32");
+  if (rc != MP_OK) return rc;
+  return cfconv_table_dispatch(a, *layout_host, flags, waves, mp::as_stream(stream));
 }
 
 // Diagnostic build of the 20-bin Gauss variant (fast softplus): adds per-phase s_memtime sums (8 x uint64,

@@ -26,8 +26,13 @@ int mp_schnet_forward_launch(const mp_schnet_forward_desc* d, mpStream_t stream)
   }
   if (rc != MP_OK) return rc;
   for (int i = 0; i < d->depth; ++i) {
-    rc = mp_cfconv_gauss_fused_f32(d->x, d->N, d->dist, d->bins, d->g_distance, d->g_sigma, d->g_offset, d->packed[i],
-                                   d->recv, d->send, nullptr, d->M, d->flags, d->agg, stream);
+    if (d->filter_table[0]) {   // the filter from the block's table (mp_cfconv_filter_table_f32), no per-edge MLP
+      rc = mp_cfconv_table_f32(d->x, d->N, d->dist, d->g_offset, d->filter_table[i], &d->filter_layout, d->recv, d->send,
+                               nullptr, d->M, d->flags & 16, 0, d->agg, nullptr, 0, stream);
+    } else {
+      rc = mp_cfconv_gauss_fused_f32(d->x, d->N, d->dist, d->bins, d->g_distance, d->g_sigma, d->g_offset, d->packed[i],
+                                     d->recv, d->send, nullptr, d->M, d->flags, d->agg, stream);
+    }
     if (rc != MP_OK) return rc;
     if (i + 1 < d->depth) {
       rc = mp_schnet_node_update_f32(d->agg, d->N, d->W2[i], d->b2[i], d->W3[i], d->b3[i], d->n, d->Wx[i + 1], d->x,

@@ -81,12 +81,32 @@ def node_weight_names(depth):
     return names
 
 
-def pack_weights(p, depth, bins, out=None):
+# The cfconv filter table (csrc/mp_cfconv.hip) of a block is used only if its self-check - largest
+# |interpolant - float64 filter| over the filter's scale - stays within TWICE the figure the MFMA kernel itself reaches
+# against float64 on the same check distances.  Measured once on an MI355X (scripts/probe_filter_table.py, seed-7 weights,
+# fast softplus): 3.43e-7, 4.01e-7 and 4.19e-7 of the scale for the three blocks - the smallest of them is taken; the
+# kernel header's 2.55e-7, a figure of the GEMMs alone, was the expectation.  The tables of the same blocks: 1.3-1.7e-7.
+FILTER_TABLE_MFMA_ERR = 3.4e-7
+FILTER_TABLE_BAR = 2.0 * FILTER_TABLE_MFMA_ERR
+FILTER_TABLE_LOG2_INV_H = 5     # spacing h = 2^-5 (a power of two: d / h is exact)
+
+
+def filter_table_layout(gauss):
+    """``mp_filter_table_layout`` of a Gauss basis, or ``None`` where the table would not fit the kernel's LDS."""
+    lay = _ffi.FilterTableLayout()
+    rc = _ffi.lib().mp_cfconv_filter_table_layout(int(gauss["bins"]), float(gauss["distance"]), float(gauss["sigma"]),
+                                                  float(gauss.get("offset", 0.0)), FILTER_TABLE_LOG2_INV_H,
+                                                  ctypes.byref(lay))
+    return lay if rc == _ffi.MP_OK else None
+
+
+def pack_weights(p, depth, bins, out=None, gauss=None):
     """Kernel-side images of the weights: ``mp_cfconv_pack_f32`` (filter MLP of every interaction block in the cfconv
     kernel's LDS order), ``mp_schnet_node_pack_f32`` (node-side matrices in register-slice order) and the node-input
     tables (``mp_schnet_embed_table_f32``: the rows the input chain writes for every node number of the vocabulary, one
     pair of tables per node build).  Packed once per weight update; ``out`` re-fills existing images in place (captured
-    graphs keep pointing at them)."""
+    graphs keep pointing at them).  With ``gauss`` (the basis arguments) every block also gets its filter table
+    (``mp_cfconv_filter_table_f32``); ``out["ftable"]["ok"]`` says whether every block's table passed its self-check."""
     nfl = _ffi.lib().mp_cfconv_packed_floats()
     rows = int(p["embedding"].shape[0]) + 1
     if out is None:
@@ -102,11 +122,25 @@ def pack_weights(p, depth, bins, out=None):
                {"node": torch.empty((2, rows, 128), dtype=torch.float32, device="cuda"),
                 "node_bf": torch.empty((2, rows, 128), dtype=torch.float32, device="cuda"),
                 "ws": torch.empty(rows, dtype=torch.float32, device="cuda")}}
+    if gauss is not None and "ftable" not in out:
+        lay = filter_table_layout(gauss)
+        out["ftable"] = None if lay is None else {
+            "layout": lay, "tables": [torch.empty(lay.rows * 128, dtype=torch.float32, device="cuda") for _ in range(depth)],
+            "check": torch.zeros((depth, 2), dtype=torch.float32, device="cuda"), "gauss": dict(gauss),
+            "ok": False, "err": None}
+    ft = out.get("ftable")
     for i in range(depth):
         pre = "interaction%d/cfconv/" % i
         _ffi.call("mp_cfconv_pack_f32", _ffi.ptr(p[pre + "dense1/kernel"]), _ffi.ptr(p.get(pre + "dense1/bias")),
                   int(bins), _ffi.ptr(p[pre + "dense2/kernel"]), _ffi.ptr(p.get(pre + "dense2/bias")),
                   _ffi.ptr(out["cfconv"][i]), _ffi.stream())
+        if ft is not None:
+            ga = ft["gauss"]
+            _ffi.call("mp_cfconv_filter_table_f32", _ffi.ptr(p[pre + "dense1/kernel"]),
+                      _ffi.ptr(p.get(pre + "dense1/bias")), int(bins), _ffi.ptr(p[pre + "dense2/kernel"]),
+                      _ffi.ptr(p.get(pre + "dense2/bias")), float(ga["distance"]), float(ga["sigma"]),
+                      float(ga.get("offset", 0.0)), ctypes.byref(ft["layout"]), _ffi.ptr(ft["tables"][i]),
+                      _ffi.ptr(ft["check"][i]), _ffi.stream())
     for k, image in out["node"].items():
         _ffi.call("mp_schnet_node_pack_f32", _ffi.ptr(p[k]), int(p[k].shape[0]), int(p[k].shape[1]), _ffi.ptr(image),
                   _ffi.stream())
@@ -122,6 +156,10 @@ def pack_weights(p, depth, bins, out=None):
                       _ffi.ptr(w["interaction0/dense1/kernel"]), _ffi.ptr(out["table"]["ws"]), _ffi.ptr(t[0]),
                       _ffi.ptr(t[1]), flags, _ffi.stream())
     torch.cuda.current_stream().synchronize()
+    if ft is not None:      # the self-check words of every block, one read-back behind the synchronisation above
+        chk = ft["check"].cpu().numpy().astype(np.float64)
+        ft["err"] = [float(e / s) if s > 0.0 else 0.0 for e, s in chk]
+        ft["ok"] = bool(np.all(np.isfinite(chk)) and all(e <= FILTER_TABLE_BAR for e in ft["err"]))
     return out
 
 
@@ -239,8 +277,11 @@ class FusedSchnet:
         # before it (use_output_mlp=False: the fork's force_schnet.py configuration)
         self.linear_head = "output_mlp/0/kernel" not in self.p
         # filter-MLP weights of every block in the cfconv kernel's LDS image order (packed once per weight update)
-        images = packed if packed is not None else pack_weights(self.p, depth, int(self.gauss["bins"]))
+        images = packed if packed is not None else pack_weights(self.p, depth, int(self.gauss["bins"]), gauss=self.gauss)
         self.packed, self.node_images = images["cfconv"], images["node"]
+        # cfconv from the blocks' filter tables where every table passed its self-check (looked up at every launch: a
+        # weight update can change the verdict); MPENGINE_FILTER_TABLE=0 keeps the MFMA kernel
+        self.ftable = images.get("ftable") if os.environ.get("MPENGINE_FILTER_TABLE", "1") != "0" else None
         # flags bit 6: node-side GEMMs on the bf16 matrix pipe (exact FP32 emulation, csrc/mp_node_tile.h) from the
         # bf16-piece images; MPENGINE_NODE_BF16=0 keeps the FP32 matrix instructions
         if "node_bf" in images and os.environ.get("MPENGINE_NODE_BF16", "1") != "0":
@@ -328,9 +369,20 @@ class FusedSchnet:
                   self.N, _ffi.ptr(b["xyz"]), _ffi.ptr(self.recv), _ffi.ptr(self.send), _ffi.ptr(self.dist),
                   _ffi.ptr(self.flags), _ffi.stream())
 
+    @property
+    def filter_table_active(self):
+        """True if the cfconv launches of this slot interpolate the filter from the blocks' tables."""
+        return self.ftable is not None and self.ftable["ok"]
+
     def _cfconv(self, i, out):
         ga = self.gauss
         recv = self.recv if self.sorted else self.recv_sorted
+        if self.filter_table_active:
+            ft = self.ftable
+            _ffi.call("mp_cfconv_table_f32", _ffi.ptr(self.x), self.N, _ffi.ptr(self.dist), float(ga["offset"]),
+                      _ffi.ptr(ft["tables"][i]), ctypes.byref(ft["layout"]), _ffi.ptr(recv), _ffi.ptr(self.send),
+                      _ffi.ptr(self.perm), self.M, self.flags_arg & 16, 0, _ffi.ptr(out), None, 0, _ffi.stream())
+            return
         _ffi.call("mp_cfconv_gauss_fused_f32", _ffi.ptr(self.x), self.N, _ffi.ptr(self.dist), int(ga["bins"]),
                   float(ga["distance"]), float(ga["sigma"]), float(ga["offset"]), _ffi.ptr(self.packed[i]),
                   _ffi.ptr(recv), _ffi.ptr(self.send), _ffi.ptr(self.perm), self.M, self.flags_arg, _ffi.ptr(out),
@@ -571,6 +623,11 @@ class FusedSchnet:
     def _descriptor_tables(self, d):
         t = self.table
         d.n_table, d.x_table = (None, None) if t is None else (t[0].data_ptr(), t[1].data_ptr())
+        on = self.filter_table_active
+        for i in range(self.depth):
+            d.filter_table[i] = self.ftable["tables"][i].data_ptr() if on else None
+        if on:
+            d.filter_layout = self.ftable["layout"]
 
     def launch_direct(self):
         """The same eight launches as the captured graph, issued directly by ONE C-ABI call on this slot's stream
@@ -628,6 +685,29 @@ class FusedSchnet:
         # algorithmic bytes of one launch: distance + ids per edge, sender rows once, output rows once
         alg_bytes = float(self.M) * (4 + 8) + 2.0 * self.N * 128 * 4
         achieved = flops / (ms * 1e-3) / 1e12
+        if self.filter_table_active:
+            # the table kernel: per edge six 512-B table rows and a 32-B entry from LDS, a 512-B sender row from L2; no
+            # matrix instruction is issued, so there is no matrix-pipe model - `achieved` stays the REFERENCE op sequence's
+            # flops over time (what bench.py compares across routes), which a kernel that executed them could not reach
+            ntiles = (self.M + 31) // 32
+            waves = 4 if ntiles <= 1024 else (8 if ntiles <= 2048 else 16)
+            lds_bytes = float(self.M) * (6 * 512 + 2 * 32)
+            l2_bytes = float(self.M) * 512 + min((ntiles + waves - 1) // waves, 256) * self.ftable["layout"].rows * 512.0
+            # bound: the union launch moves 96 MB through L2 (sender rows, 109 KB of table per workgroup) in 11.5 us,
+            # 8.3 TB/s with the ~4 us launch floor inside, against 17-19 TB/s for rows gathered from L2; its LDS reads run
+            # at 36 TB/s of 157 (profiles/r05_table_*) - L2 is the nearer limit
+            return {"bound": "l2", "kernel": "cfconv_table_kernel<%d> (SchNetCFconv from the block's filter table, one "
+                                              "interaction block)" % waves,
+                    "achieved": achieved, "peak": mfma_peak_tf, "unit": "TFLOP/s (reference op sequence)",
+                    "frac": achieved / mfma_peak_tf, "traffic": None, "avg_launch_us": ms * 1e3,
+                    "algorithmic_flops_per_launch": flops, "algorithmic_bytes_per_launch": alg_bytes,
+                    "lds_bytes_per_launch": lds_bytes, "lds_gbs_at_this_rate": lds_bytes / (ms * 1e-3) / 1e9,
+                    "l2_bytes_per_launch": l2_bytes, "l2_gbs_at_this_rate": l2_bytes / (ms * 1e-3) / 1e9,
+                    "hbm_gbs_at_this_rate": alg_bytes / (ms * 1e-3) / 1e9, "hbm_peak_gbs": hbm_peak_gbs,
+                    "filter_table_error": list(self.ftable["err"]),
+                    "peak_note": "the filter MLP is not executed per edge: its 38.1 kflop per edge are replaced by a "
+                                 "six-point interpolation in a per-block table (DESIGN.md 3.28); achieved / frac count the "
+                                 "reference op sequence's flops and may exceed the matrix peak"}
         # matrix-pipe occupancy of the instruction mix actually issued, per 32-edge tile: GEMM2 = 8 k blocks x 4 column
         # blocks x 6 v_mfma_f32_32x32x16_bf16 (32 cycles each; FP32 emulated exactly from three bf16 pieces per operand);
         # GEMM1 = 2 k blocks x 4 hidden blocks x 6 of the same (basis + bias row <= 32 slots: 20 bins), else
@@ -824,9 +904,15 @@ class SchnetFusedRoute:
             self._arena.clear()    # cached descriptors hold the old weight addresses
             self._grad_images = None
             self._p = {k: v for k, v in p.items() if v is not None}
-            self._packed = pack_weights(self._p, self.depth, int(self.gauss["bins"]))
+            self._packed = pack_weights(self._p, self.depth, int(self.gauss["bins"]), gauss=self.gauss)
         else:                      # same tensors, new values: re-fill the images the graphs already point at
+            ft = self._packed.get("ftable")
+            was = ft is not None and ft["ok"]
             pack_weights(self._p, self.depth, int(self.gauss["bins"]), out=self._packed)
+            if ft is not None and ft["ok"] != was:   # the other cfconv kernel from now on: captured graphs name the old
+                for slot in list(self._slots.values()) + [g.slot for g in self._groups.values()]:   # one, slots re-capture
+                    slot._drop_graphs()
+                    slot._desc = slot._desc_ref = None    # (re-made from the work set's descriptor, table fields re-set)
             if self._grad_images is not None:
                 from .fused_schnet_force import make_grad_images
                 make_grad_images(self._p, self.depth, int(self.gauss["bins"]), "output_mlp/0/kernel" not in self._p,
@@ -969,6 +1055,13 @@ class SchnetFusedRoute:
                 return got
         eng, force = slot.run_current(how)
         return (eng.clone(), force.clone()) if self.copy_output else (eng, force)
+
+    @property
+    def filter_table_active(self):
+        """True if the inference forward takes the cfconv filter from the blocks' tables (every table passed its
+        self-check at the last weight update and MPENGINE_FILTER_TABLE is not 0); False: the MFMA kernel runs."""
+        ft = None if self._packed is None else self._packed.get("ftable")
+        return bool(ft is not None and ft["ok"] and os.environ.get("MPENGINE_FILTER_TABLE", "1") != "0")
 
     def slot_of(self, inputs):
         return self._slots.get(self._key(*inputs))

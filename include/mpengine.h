@@ -292,6 +292,34 @@ int mp_cfconv_gauss_fused_ws_f32(const float* x, int64_t N, const float* dist, i
                                  const int32_t* perm, int64_t M, int flags, float* out_zeroed, void* ws, size_t ws_bytes,
                                  mpStream_t stream);
 
+/* Inference route of the Gauss variant: the filter w(d) = Dense(Dense(gauss(d))) of a block is a function of the block's
+ * weights and of the edge distance alone, so it is tabulated once per weight update and the kernel interpolates it
+ * (six-point Lagrange on a power-of-two grid; no per-edge MLP).  Row j of the table holds the 128 filter values at the
+ * knot v_lo + (j - 2) / inv_h of v = d - offset, evaluated in double precision and rounded to float once; v is clamped
+ * to [v_lo, v_end], beyond which the filter is constant to 2.3e-11 of a unit weight.
+ *   mp_cfconv_filter_table_layout  host only: domain v_lo = max(-offset, -7 sigma) .. distance (bins-1)/bins + 7 sigma,
+ *                                  spacing 2^-log2_inv_h; MP_EINVAL if the table would exceed MP_FILTER_TABLE_MAX_ROWS.
+ *   mp_cfconv_filter_table_f32     fills table (layout->rows x 128 floats) and check2: [0] the largest |interpolant -
+ *                                  double filter| over the quarter, half and three-quarter points of every interval and
+ *                                  four points beyond the ends, the interpolant evaluated with the kernel's arithmetic;
+ *                                  [1] the largest |filter| there.  The caller decides from check2 whether to use the table.
+ *   mp_cfconv_table_f32            the forward kernel (same tiles, segment rule, flags bits 4 and 5 and workspace as
+ *                                  mp_cfconv_gauss_fused_ws_f32); waves per workgroup 4, 8, 16 or 0 = by tile count. */
+#define MP_FILTER_TABLE_MAX_ROWS 256
+typedef struct mp_filter_table_layout {
+  float v_lo, v_end, inv_h;   /* domain of v = d - offset, 1 / spacing (a power of two) */
+  int32_t n_int, rows;        /* intervals; rows = n_int + 5, padded to even */
+} mp_filter_table_layout;
+int mp_cfconv_filter_table_layout(int bins, float distance, float sigma, float offset, int log2_inv_h,
+                                  mp_filter_table_layout* layout_out_host);
+int mp_cfconv_filter_table_f32(const float* W1, const float* b1, int B, const float* W2, const float* b2, float distance,
+                               float sigma, float offset, const mp_filter_table_layout* layout_host, float* table,
+                               float* check2, mpStream_t stream);
+int mp_cfconv_table_f32(const float* x, int64_t N, const float* dist, float offset, const float* table,
+                        const mp_filter_table_layout* layout_host, const int32_t* recv_sorted, const int32_t* send,
+                        const int32_t* perm, int64_t M, int flags, int waves, float* out_zeroed, void* ws, size_t ws_bytes,
+                        mpStream_t stream);
+
 /* Reverse pass of SchNetCFconv for forces (kgcnn/model/force.py:159-177 through schnet_conv.py:73-79, geom.py:567-571).
  * dE/dx_j is the forward kernel itself with the two index columns swapped (g_out in place of x, the sender-sorted list in
  * place of the receiver-sorted one).  mp_cfconv_gauss_dist_grad_f32 is the other half: per edge (original order)
@@ -621,6 +649,9 @@ typedef struct mp_schnet_forward_desc {
   int32_t* recv; int32_t* send; float* dist; int32_t* flags_word;           /* (M) work buffers, flag word */
   float* n; float* x; float* agg; float* h; float* out;                     /* (N,128) x3 [agg zeroed], (N,64), (G,1) */
   const float* n_table; const float* x_table;   /* mp_schnet_embed_table_f32 tables; NULL: stage 0 runs the chain */
+  /* interaction i: mp_cfconv_filter_table_f32 table; [0] == NULL: every block runs the MFMA kernel from packed[i] */
+  const float* filter_table[MP_SCHNET_MAX_DEPTH];
+  mp_filter_table_layout filter_layout;
 } mp_schnet_forward_desc;
 int mp_schnet_forward_launch(const mp_schnet_forward_desc* desc_host, mpStream_t stream);
 
