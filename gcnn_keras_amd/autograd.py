@@ -1247,7 +1247,8 @@ class DirectedEdgeUpdate(torch.autograd.Function):
 # First-order rule of the fused importance readout (literature/MEGAN.py; csrc/mp_megan.hip): two launches forward, two
 # in reverse, whatever the number of channels and attention layers.
 
-MEGAN_READOUT_SIZES = {"max_channels": 8, "max_layers": 8, "max_width": 512}   # include/mpengine.h MP_MEGAN_*
+MEGAN_READOUT_SIZES = {"max_channels": _ffi.MP_MEGAN_MAX_CHANNELS, "max_layers": _ffi.MP_MEGAN_MAX_LAYERS,
+                       "max_width": _ffi.MP_MEGAN_MAX_WIDTH}
 
 
 def megan_readout_values(x, z, plan, row_splits, g_rows, op, logits, want_p=False):
