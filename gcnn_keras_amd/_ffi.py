@@ -4,11 +4,11 @@ This is the only place where Python meets the engine: plain pointers and sizes c
 for device memory and streams only.  There is NO CPU fallback: if the shared library is missing or a tensor is
 not on a HIP device, the call fails loudly.
 
-Nothing of the ABI is written down here.  The header (and behind it every model header of ``MODEL_HEADERS``, such as
-include/mpengine_hamnet.h) is read once at import (``_header.parse``, strict: a declaration
-it does not understand is an error) and gives every ``MP_*`` constant as a module attribute, the descriptor structs as
-``ctypes.Structure`` classes and the argument and return types of every entry point.  A new entry point is declared in
-a header and defined in csrc/, nowhere else.
+Nothing of the ABI is written down here.  The umbrella header and the family headers it includes (include/mpengine/*.h)
+are read once at import (``_header.expand`` and ``_header.parse``, strict: a declaration it does not understand is an
+error) and give every ``MP_*`` constant as a module attribute, the descriptor structs as ``ctypes.Structure`` classes and
+the argument and return types of every entry point.  A new entry point is declared in a family header and defined in
+csrc/, nowhere else.
 """
 import ctypes
 import os
@@ -20,33 +20,13 @@ from . import _header
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libmpengine.so")
-HEADER_PATH = os.path.join(_HERE, "..", "include", "mpengine.h")   # where csrc/mp_common.h includes it from
+HEADER_PATH = os.path.join(_HERE, "..", "include", "mpengine.h")   # the umbrella over include/mpengine/*.h
 
-MODEL_HEADERS = ("mpengine_hamnet.h",)   # model headers beside mpengine.h: they include it and add entry points
-
-with open(HEADER_PATH) as _file:
-    _BASE_TEXT = _file.read()
-_ABI = _header.parse(_BASE_TEXT)
-
-
-def _model_abi():
-    """Constants and prototypes the model headers add: each is parsed behind mpengine.h's text (its types and constants
-    are the ones a model header uses), and what mpengine.h itself declares is taken out again."""
-    constants, signatures, restypes = {}, {}, {}
-    for name in MODEL_HEADERS:
-        with open(os.path.join(os.path.dirname(HEADER_PATH), name)) as file:
-            both = _header.parse(_BASE_TEXT + "\n" + file.read())
-        constants.update({k: v for k, v in both.constants.items() if k not in _ABI.constants})
-        signatures.update({k: v for k, v in both.signatures.items() if k not in _ABI.signatures})
-        restypes.update({k: v for k, v in both.restypes.items() if k not in _ABI.restypes})
-    return constants, signatures, restypes
-
-
-_MODEL_CONSTANTS, _MODEL_SIGNATURES, _MODEL_RESTYPES = _model_abi()
+HEADER_TEXT = _header.expand(HEADER_PATH)   # the umbrella with every family header in place of its #include
+_ABI = _header.parse(HEADER_TEXT)
 
 globals().update(_ABI.constants)   # MP_OK, MP_EINVAL, MP_SUM, MP_ACT_*, MP_SCHNET_MAX_DEPTH, ...: every constant
-globals().update(_MODEL_CONSTANTS)  # MP_HAMNET_MAX_DEPTH, ...
-_SIGNATURES = _ABI.signatures      # name -> argtypes, of mpengine.h
+_SIGNATURES = _ABI.signatures      # name -> argtypes
 _RESTYPES = {name: restype for name, restype in _ABI.restypes.items() if restype is not c_int}   # int unless listed
 
 FilterTableLayout = _ABI.structs["mp_filter_table_layout"]
@@ -79,13 +59,8 @@ class EngineError(RuntimeError):
 
 
 def declared_symbols():
-    """Names of every entry point declared in include/mpengine.h (checked by tests/test_abi.py)."""
+    """Names of every entry point declared under include/mpengine.h (checked by tests/test_abi.py)."""
     return sorted(_SIGNATURES)
-
-
-def model_symbols():
-    """Names of every entry point declared in the model headers (``MODEL_HEADERS``)."""
-    return sorted(_MODEL_SIGNATURES)
 
 
 def lib():
@@ -100,14 +75,14 @@ def lib():
             raise EngineError("libmpengine.so not found at %s - build it with __graft_entry__.build() "
                               "(there is no CPU fallback)" % path)
         handle = ctypes.CDLL(path)
-        for name, argtypes in list(_SIGNATURES.items()) + list(_MODEL_SIGNATURES.items()):
+        for name, argtypes in _SIGNATURES.items():
             fn = getattr(handle, name, None)
             if fn is None:
                 if path == LIB_PATH:
                     raise EngineError("libmpengine.so lacks %s - rebuild it (__graft_entry__.build())" % name)
                 continue
             fn.argtypes = argtypes
-            fn.restype = _RESTYPES.get(name, _MODEL_RESTYPES.get(name, c_int))
+            fn.restype = _RESTYPES.get(name, c_int)
         _lib = handle
     return _lib
 

@@ -1,12 +1,14 @@
-"""Strict parser of include/mpengine.h: the header is the one declaration of the C ABI, ``_ffi`` derives its ctypes
-tables from it.
+"""Strict parser of include/mpengine.h and the family headers it includes: they are the one declaration of the C ABI,
+``_ffi`` derives its ctypes tables from them.
 
-``parse(text)`` understands exactly what the header uses - ``#define MP_*`` integer constants, ``enum``s, a ``typedef``
+``expand(path)`` gives a header's text with every quoted ``#include`` replaced by the text of that file; ``parse(text)``
+understands exactly what the header uses - ``#define MP_*`` integer constants, ``enum``s, a ``typedef``
 of a pointer, ``typedef struct name { ... } name;`` and prototypes returning ``int`` or ``const char*`` - and raises
 ``HeaderError`` naming the declaration for anything else: a wrong guess here would hand a kernel a wrong device pointer.
 """
 import collections
 import ctypes
+import os
 import re
 
 # C type -> ctypes type of a parameter or field.  Every pointer is c_void_p, except a char* parameter (c_char_p).
@@ -28,7 +30,26 @@ _BLOCK = re.compile(r"(enum|typedef struct)\s+(%s)\s*\{(.*)\}\s*(\w*)" % _NAME)
 _PROTOTYPE = re.compile(r"([^()]+)\(([^()]*)\)")
 _DECLARATOR = re.compile(r"\s*(?:((?:%s\s+)*%s)(?=[\s*]))?\s*((?:\*\s*)*)(%s)\s*(?:\[([^\][]*)\])?\s*"
                          % (_NAME, _NAME, _NAME))
+_QUOTED_INCLUDE = re.compile(r'^[ \t]*#[ \t]*include[ \t]*"([^"\n]*)"[^\n]*$', re.M)
 _EXPR_TOKEN = re.compile(r"0[xX][0-9a-fA-F]+|\d+|(%s)|<<|>>|[-+*/%%|&^~()]" % _NAME)
+
+
+def expand(path, seen=None):
+    """Text of the header ``path`` with every line ``#include "x.h"`` replaced by the text of x.h, looked up beside the
+    including file.  A file is read once: a repeated include, or one that closes a cycle, expands to nothing."""
+    seen = set() if seen is None else seen
+    if os.path.realpath(path) in seen:
+        return ""
+    seen.add(os.path.realpath(path))
+    with open(path) as file:
+        text = file.read()
+
+    def included(found):
+        target = os.path.join(os.path.dirname(path), found.group(1))
+        if not os.path.isfile(target):
+            raise HeaderError('%s: #include "%s": no such file' % (path, found.group(1)))
+        return expand(target, seen)
+    return _QUOTED_INCLUDE.sub(included, text)
 
 
 def _integer(expr, constants, where):
@@ -136,8 +157,8 @@ def parse(text):
             constants[define.group(1)] = _integer(define.group(2), constants, "#define " + define.group(1))
         elif define and define.group(2).strip():
             raise HeaderError("%r: only MP_* integer constants are bound" % decl)
-        elif decl.startswith("#"):   # the include guard and #include pass; a conditional section would be read as live
-            if not re.match(r"#\s*(include|ifndef|define|endif)\b", decl):
+        elif decl.startswith("#"):   # include guards and #include <...> pass; a conditional section would be read as live
+            if not re.match(r"#\s*(include\s*<|ifndef\b|define\b|endif\b)", decl):   # #include "x.h": expand() comes first
                 raise HeaderError("%r: directive not understood" % decl)
         elif block and block.group(1) == "enum" and not block.group(4):
             _enum(block.group(2), block.group(3), constants)

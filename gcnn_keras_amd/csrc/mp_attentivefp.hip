@@ -49,6 +49,7 @@
 #include "mp_attend.h"
 #include "mp_common.h"
 #include "mp_edge_tile.h"
+#include "../../include/mpengine/attentivefp.h"
 
 #include <type_traits>
 

@@ -3,6 +3,7 @@
 // the gathered column, segment-sum-backward = gather by the receiver ids, dense-backward = dense with the transposed
 // kernel); this file holds the elementwise derivatives that have no forward counterpart.
 #include "mp_common.h"
+#include "../../include/mpengine/backward.h"
 
 namespace {
 

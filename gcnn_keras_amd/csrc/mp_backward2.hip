@@ -5,6 +5,7 @@
 // derivative of mp_backward.hip.  This file holds the reverse of the latter: for y = g * f'(x) and an upstream h on y,
 // g_bar = h * f'(x) and x_bar = h * g * f''(x), both from one pass over the saved inputs.  Either output may be NULL.
 #include "mp_common.h"
+#include "../../include/mpengine/backward.h"
 
 namespace {
 

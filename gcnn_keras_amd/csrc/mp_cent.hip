@@ -27,6 +27,7 @@
 #include <math.h>
 
 #include "mp_common.h"
+#include "../../include/mpengine/hdnnp.h"
 
 namespace {
 

@@ -55,6 +55,7 @@
 #include <type_traits>
 
 #include "mp_common.h"
+#include "../../include/mpengine/schnet.h"
 
 namespace {
 

@@ -23,6 +23,7 @@
 // bases) + the three W2 images = 137 KB, staged by LDS-DMA.
 
 #include "mp_common.h"
+#include "../../include/mpengine/schnet.h"
 
 namespace {
 

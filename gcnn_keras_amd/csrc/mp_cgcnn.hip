@@ -25,6 +25,7 @@
 // a node without edges has u = 0, and BN_out(0) = beta - mean * inv is NOT zero.
 #include "mp_common.h"
 #include "mp_edge_tile.h"
+#include "../../include/mpengine/cgcnn.h"
 
 namespace {
 

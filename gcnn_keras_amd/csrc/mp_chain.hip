@@ -15,6 +15,8 @@
 // W1 / W2 are mp_chain_pack_f32 images: the k-major register order of one wave's column slice, 16-B loads.
 
 #include "mp_common.h"
+#include "../../include/mpengine/chain.h"
+#include "../../include/mpengine/painn.h"
 
 namespace {
 

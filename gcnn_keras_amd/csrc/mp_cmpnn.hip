@@ -21,6 +21,7 @@
 #include <type_traits>
 
 #include "mp_common.h"
+#include "../../include/mpengine/cmpnn.h"
 
 namespace {
 

@@ -7,7 +7,7 @@
 #include <cstdio>
 #include <mutex>
 
-#include "../../include/mpengine.h"
+#include "../../include/mpengine/core.h"
 
 namespace mp {
 

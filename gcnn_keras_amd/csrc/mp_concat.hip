@@ -8,6 +8,7 @@
 // the weight staging once.  Measured (bench.py): four 128-graph batches per launch group, two or three groups in flight:
 // 860-900 M edges/s against 757 M for four separate forwards in flight.
 #include "mp_common.h"
+#include "../../include/mpengine/batching.h"
 
 namespace {
 

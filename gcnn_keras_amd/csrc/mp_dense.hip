@@ -10,6 +10,7 @@
 // The fused SchNet kernels (mp_cfconv.hip / mp_schnet_node.hip) are the throughput path; this kernel serves
 // the layer-by-layer API and the GEMMs that are not worth fusing.
 #include "mp_common.h"
+#include "../../include/mpengine/dense.h"
 
 namespace {
 

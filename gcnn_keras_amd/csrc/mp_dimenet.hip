@@ -13,6 +13,7 @@
 #include <math.h>
 
 #include "mp_common.h"
+#include "../../include/mpengine/dimenet.h"
 
 namespace {
 

@@ -19,6 +19,8 @@
 // gather as a segment sum over the CSR of rev (edges without a reverse lie in the extra segment E, which nobody reads):
 // right for any rev, an involution or not.  One work item owns (edge, 16-byte chunk); rows are added in CSR order.
 #include "mp_common.h"
+#include "../../include/mpengine/cmpnn.h"
+#include "../../include/mpengine/dmpnn.h"
 
 namespace {
 

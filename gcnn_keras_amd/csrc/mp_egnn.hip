@@ -26,6 +26,7 @@
 // over the two CSRs (host side), in list order.
 #include "mp_common.h"
 #include "mp_edge_tile.h"
+#include "../../include/mpengine/egnn.h"
 
 namespace {
 

@@ -2,6 +2,8 @@
 // the geometry pre-step (kgcnn/layers/geom.py lines cited per function) and ChangeTensorType
 // (kgcnn/layers/casting.py:79-84).  All HBM-bound streaming kernels: grid-stride, coalesced, one pass.
 #include "mp_common.h"
+#include "../../include/mpengine/dense.h"
+#include "../../include/mpengine/geometry.h"
 
 namespace {
 

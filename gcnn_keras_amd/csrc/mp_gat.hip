@@ -54,6 +54,7 @@
 // tensor itself.
 #include "mp_common.h"
 #include "mp_edge_tile.h"
+#include "../../include/mpengine/gat.h"
 
 namespace {
 

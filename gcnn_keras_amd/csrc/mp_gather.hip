@@ -6,6 +6,7 @@
 // accesses (2 rows per wave64 instruction).  The node table (1.2 MB at config 2, 58 MB per GPU at config 4) is
 // L2 / Infinity-Cache resident, the (M, .) output stream is the HBM traffic.
 #include "mp_common.h"
+#include "../../include/mpengine/gather.h"
 
 namespace {
 

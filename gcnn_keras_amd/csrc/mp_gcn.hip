@@ -25,6 +25,7 @@
 #include <type_traits>
 
 #include "mp_common.h"
+#include "../../include/mpengine/gcn.h"
 
 namespace {
 

@@ -49,8 +49,7 @@
 //   A graph without nodes starts from s = 0 and has m = act_attend(0) in every iteration, as the layer sequence has.
 #include "mp_common.h"
 #include "mp_edge_tile.h"
-
-#include "../../include/mpengine_hamnet.h"
+#include "../../include/mpengine/hamnet.h"
 
 namespace {
 

@@ -10,6 +10,8 @@
 
 #include "mp_common.h"
 #include "mp_edge_prepare.h"
+#include "../../include/mpengine/index.h"
+#include "../../include/mpengine/schnet.h"
 
 namespace {
 

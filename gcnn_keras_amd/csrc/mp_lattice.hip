@@ -25,6 +25,8 @@
 #include <rocprim/rocprim.hpp>
 
 #include "mp_common.h"
+#include "../../include/mpengine/cgcnn.h"
+#include "../../include/mpengine/geometry.h"
 
 namespace {
 

@@ -37,6 +37,7 @@
 // out[i] = h[i] + y[i] @ Wm with Wm (C, E) ("concat") or (U, E) applied to every head's columns ("sum": the sum over
 // heads of y_h @ Wm is (sum_h y_h) @ Wm); y is never written.
 #include "mp_common.h"
+#include "../../include/mpengine/mat.h"
 
 namespace {
 

@@ -24,6 +24,7 @@
 // the edge importances is a gather per (edge, channel), not the adjoint scatter, because the mean pools' adjoints
 // broadcast a node value to the edges of its list.
 #include "mp_common.h"
+#include "../../include/mpengine/megan.h"
 
 namespace {
 

@@ -24,6 +24,7 @@
 // and divides by the edge count for the mean.
 #include "mp_common.h"
 #include "mp_edge_tile.h"
+#include "../../include/mpengine/megnet.h"
 
 namespace {
 

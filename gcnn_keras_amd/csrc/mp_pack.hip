@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "mp_common.h"
+#include "../../include/mpengine/batching.h"
 
 namespace {
 

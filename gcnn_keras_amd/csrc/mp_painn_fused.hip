@@ -23,6 +23,7 @@
 
 #include "mp_common.h"
 #include "mp_edge_prepare.h"
+#include "../../include/mpengine/painn.h"
 
 namespace {
 

@@ -16,6 +16,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "mp_common.h"
+#include "../../include/mpengine/geometry.h"
 
 namespace {
 

@@ -9,6 +9,7 @@
 // forward's row reads (k fixed, c = lane) and the reverse's column reads (c fixed, k = lane) are bank-conflict free -
 // and the pooled / gradient vectors are broadcast with v_readlane.  Sequential node order (tf.math.segment_sum's).
 #include "mp_common.h"
+#include "../../include/mpengine/chain.h"
 
 namespace {
 

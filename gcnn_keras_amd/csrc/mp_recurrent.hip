@@ -11,6 +11,8 @@
 #include <type_traits>
 
 #include "mp_common.h"
+#include "../../include/mpengine/cmpnn.h"
+#include "../../include/mpengine/recurrent.h"
 
 namespace {
 

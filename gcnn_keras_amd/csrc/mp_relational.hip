@@ -14,6 +14,8 @@
 // relation's rows in row order: the same bits every run and on every stream.  Nothing is read back to the host, so a
 // captured HIP graph replays every call.
 #include "mp_common.h"
+#include "../../include/mpengine/hdnnp.h"
+#include "../../include/mpengine/index.h"
 
 namespace {
 

@@ -33,6 +33,7 @@
 #include <type_traits>
 
 #include "mp_common.h"
+#include "../../include/mpengine/rgcn.h"
 
 namespace {
 

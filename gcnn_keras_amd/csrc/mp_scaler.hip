@@ -23,6 +23,7 @@
 #include <math.h>
 
 #include "mp_common.h"
+#include "../../include/mpengine/scaler.h"
 
 namespace {
 

@@ -15,6 +15,8 @@
 // swapped index columns (dE/dx_j); the force kernel at the end turns dE/dd into -dE/dx over both CSRs.
 #include "mp_common.h"
 #include "mp_node_tile.h"
+#include "../../include/mpengine/schnet.h"
+#include "../../include/mpengine/schnet_model.h"
 
 namespace {
 

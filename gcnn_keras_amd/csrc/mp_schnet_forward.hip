@@ -7,6 +7,8 @@
 // holds no lock, so several batch slots can be fed by a host thread each.  (With four slots in flight both paths run at
 // the same 46-47 us per step on an MI355X: there the GPU is the limit, not the submission path.)
 #include "mp_common.h"
+#include "../../include/mpengine/schnet.h"
+#include "../../include/mpengine/schnet_model.h"
 
 extern "C" {
 

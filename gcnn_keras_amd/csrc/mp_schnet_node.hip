@@ -18,6 +18,8 @@
 #include "mp_common.h"
 #include "mp_edge_prepare.h"
 #include "mp_node_tile.h"
+#include "../../include/mpengine/schnet.h"
+#include "../../include/mpengine/schnet_model.h"
 
 // Diagnostic build (make diag -> libmpengine_diag.so, scripts/probe_node_diag.py): cycle stamps around the phases of the
 // node-update tile loop.  Compiles to nothing in the product library.
@@ -645,6 +647,7 @@ void launch_stage0(const NodeArgs& a, const mp_prep::EdgePrepArgs& p, int node_b
 extern "C" {
 
 #ifdef MP_NODE_DIAG
+int mp_debug_node_diag(unsigned long long* out8_host);   // no header declares it: it is not part of the ABI
 int mp_debug_node_diag(unsigned long long* out8_host) {  // diagnostic build only: read and clear the phase sums
   MP_HIP(hipMemcpyFromSymbol(out8_host, HIP_SYMBOL(g_node_diag), 64));
   const unsigned long long zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};

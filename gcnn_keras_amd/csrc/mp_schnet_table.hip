@@ -12,6 +12,8 @@
 // node-number load of a step is issued before the first row load, every row load before the first store.
 #include "mp_common.h"
 #include "mp_edge_prepare.h"
+#include "../../include/mpengine/schnet.h"
+#include "../../include/mpengine/schnet_model.h"
 
 namespace {
 

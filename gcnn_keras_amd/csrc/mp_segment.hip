@@ -14,6 +14,7 @@
 #include <type_traits>
 
 #include "mp_common.h"
+#include "../../include/mpengine/segment.h"
 
 namespace {
 

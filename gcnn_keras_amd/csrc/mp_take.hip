@@ -15,6 +15,7 @@
 //                           its own (a unit of 4-byte rows can span several graphs; (N, 3) coordinates start most graphs
 //                           off a 16-byte boundary).  Every offset is 64-bit; nothing is written past dst_rows rows.
 #include "mp_common.h"
+#include "../../include/mpengine/batching.h"
 
 namespace {
 

@@ -25,6 +25,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "mp_common.h"
+#include "../../include/mpengine/topk.h"
 
 namespace {
 

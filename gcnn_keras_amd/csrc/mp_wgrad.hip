@@ -19,6 +19,10 @@
 // order.  The bias sum is taken from the G tiles already staged (workgroups of K-tile 0).  No atomics: the result is
 // the same bits on every run and every stream.
 #include "mp_common.h"
+#include "../../include/mpengine/dmpnn.h"
+#include "../../include/mpengine/index.h"
+#include "../../include/mpengine/segment.h"
+#include "../../include/mpengine/wgrad.h"
 
 namespace {
 

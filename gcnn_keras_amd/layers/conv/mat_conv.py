@@ -31,7 +31,7 @@ from ..modules import Dense, dense_values
 TRAFO_CODES = {None: _ffi.MP_MAT_TRAFO_NONE, "exp": _ffi.MP_MAT_TRAFO_EXP, "softmax": _ffi.MP_MAT_TRAFO_SOFTMAX}
 MERGE_SUM_NAMES = ("add", "sum", "reduce_sum")   # kgcnn/literature/MAT.py:169; anything else concatenates
 
-# csrc/mp_mat.hip, include/mpengine.h: the tiles of the kernel and the caps of its merge epilogue
+# csrc/mp_mat.hip, include/mpengine/mat.h: the tiles of the kernel and the caps of its merge epilogue
 FUSED_MAT_SIZES = {"units_multiple": 4, "max_channels": _ffi.MP_MAT_EPILOGUE_MAX_CHANNELS,
                    "max_width": _ffi.MP_MAT_EPILOGUE_MAX_WIDTH,
                    "receiver_tile": _ffi.MP_MAT_RECV_TILE, "sender_tile": _ffi.MP_MAT_SEND_TILE}

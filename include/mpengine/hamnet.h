@@ -1,14 +1,12 @@
 /*
- * mpengine_hamnet.h - the HamNet entry points of libmpengine.so (csrc/mp_hamnet.hip).
- *
- * A model header beside mpengine.h, whose conventions hold here: device pointers unless the name ends in _host, calls
- * asynchronous on the caller's stream, MP_OK or a negative status.  The ctypes binding (gcnn_keras_amd/_ffi.py) reads
- * this header behind mpengine.h with the same strict parser.
+ * mpengine/hamnet.h - HamNet.
+ * Defined in csrc/: mp_hamnet.hip.
+ * Part of the C ABI of libmpengine.so: the conventions are stated in mpengine.h, the umbrella.
  */
 #ifndef MPENGINE_HAMNET_H
 #define MPENGINE_HAMNET_H
 
-#include "mpengine.h"
+#include "core.h"
 
 #ifdef __cplusplus
 extern "C" {

@@ -352,7 +352,7 @@ def kernel_case(sizes, heads, units, trafo="exp", edges="sorted", add_identity=F
             "lg": lambda_adjacency(la, ld, lg), "add_identity": add_identity, "edges": edges}
 
 
-R, S = 16, 64   # MP_MAT_RECV_TILE, MP_MAT_SEND_TILE (include/mpengine.h; the tests check that they still are)
+R, S = 16, 64   # MP_MAT_RECV_TILE, MP_MAT_SEND_TILE (include/mpengine/mat.h; the tests check that they still are)
 MIXED = (0, 1, 3, R + 1, 0, S + 2, 0)   # empty graphs first, in the middle and last
 
 

@@ -247,7 +247,7 @@ def model_restate(params, cfg, b, dtype, requires_grad=False):
 
 
 # ----------------------------------------------------------------------------------------------- kernel cases
-NODE_TILE = 64   # MP_MEGAN_NODE_TILE of include/mpengine.h
+NODE_TILE = 64   # MP_MEGAN_NODE_TILE of include/mpengine/megan.h
 
 
 def directed_edges():

@@ -29,7 +29,7 @@ def _sigmoid(x):
 
 
 def act(code, x, alpha=ALPHA):
-    """Activation ``code`` of include/mpengine.h in the dtype of ``x``."""
+    """Activation ``code`` of include/mpengine/core.h in the dtype of ``x``."""
     x = np.asarray(x)
     t = x.dtype.type
     if code == 0:

@@ -1,6 +1,7 @@
-"""The C-ABI library loads and exports every symbol include/mpengine.h declares; the ctypes binding derived from the
-header (gcnn_keras_amd/_header.py) is the header's, literally and against the C compiler; argument errors map to Python
-exceptions.  No compute is launched (runs without a GPU)."""
+"""The C-ABI library loads and exports exactly the symbols that include/mpengine.h, the umbrella over the family headers
+of include/mpengine/, declares; the ctypes binding derived from the headers (gcnn_keras_amd/_header.py) is theirs,
+literally and against the C compiler; argument errors map to Python exceptions.  No compute is launched (runs without a
+GPU)."""
 import ctypes
 import os
 import re
@@ -16,8 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _header_symbols():
-    text = open(os.path.join(ROOT, "include", "mpengine.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"/\*.*?\*/", "", _ffi.HEADER_TEXT, flags=re.S)
     return sorted(set(re.findall(r"\b(mp_[a-z0-9_]+)\s*\(", text)))
 
 
@@ -35,11 +35,22 @@ def test_every_declared_symbol_is_exported():
         assert hasattr(lib, name), name
 
 
+def test_library_exports_only_what_the_headers_declare():
+    """The mp_* names of the dynamic symbol table are the declared ones, no more: a definition without a declaration
+    does not compile (-Werror=missing-prototypes), and nothing else may leak out under the prefix."""
+    nm = shutil.which("nm")
+    if nm is None:
+        pytest.skip("no nm")
+    table = subprocess.run([nm, "-D", "--defined-only", _ffi.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    exported = sorted(line.split()[-1] for line in table.splitlines() if line.split()[-1].startswith("mp_"))
+    assert exported == _ffi.declared_symbols()
+
+
 def test_signatures_are_the_headers_literally():
     """Argument lists as the hand-written table had them, one per kind of type the header uses."""
     P, i, i64, f = c_void_p, c_int, c_int64, c_float
     sig = _ffi._SIGNATURES
-    assert len(sig) == 195
+    assert len(sig) == 198
     assert sig["mp_last_error"] == [] and _ffi._RESTYPES == {"mp_last_error": c_char_p}
     assert sig["mp_cfconv_packed_floats"] == []
     assert sig["mp_device_info"] == [c_char_p, i, P, P]
@@ -113,6 +124,46 @@ def test_parser_on_a_synthetic_header():
     assert h.restypes["mp_go"] is c_int
 
 
+def _write(folder, **files):
+    for name, text in files.items():
+        (folder / (name + ".h")).write_text(text)
+    return str(folder / "all.h")
+
+
+def test_parser_follows_quoted_includes(tmp_path):
+    """An umbrella over two files, the second of which includes the first again: every declaration once, in include
+    order, and a constant of the first file sizes a field of the second."""
+    (tmp_path / "sub").mkdir()
+    umbrella = _write(tmp_path, all='/* umbrella */\n#include <stdint.h>\n#include "sub/a.h"\n  #  include "sub/b.h" /* b */\n')
+    _write(tmp_path / "sub",
+           a='#ifndef A_H\n#define A_H\n#include <stddef.h>\n#define MP_N 3\ntypedef void* mpStream_t;\n'
+             'int mp_first(int a, mpStream_t stream);\n#endif\n',
+           b='#ifndef B_H\n#define B_H\n#include "a.h"\ntypedef struct mp_s { float f[MP_N + 1]; } mp_s;\n'
+             'int mp_second(const mp_s* desc_host);\n#include "../all.h"\n#endif\n')
+    text = _header.expand(umbrella)
+    assert text.count("mp_first") == 1 and '#include "' not in text and "#include <stdint.h>" in text
+    h = _header.parse(text)
+    assert list(h.signatures) == ["mp_first", "mp_second"] and h.constants == {"MP_N": 3}
+    assert h.signatures["mp_first"] == [c_int, c_void_p] and h.signatures["mp_second"] == [c_void_p]
+    assert ctypes.sizeof(h.structs["mp_s"]) == 16
+
+
+def test_parser_names_an_include_it_cannot_resolve(tmp_path):
+    umbrella = _write(tmp_path, all='#include "here.h"\n#include "sub/missing.h"\n', here="int mp_f(void);\n")
+    with pytest.raises(_header.HeaderError) as raised:
+        _header.expand(umbrella)
+    assert "sub/missing.h" in str(raised.value)
+    with pytest.raises(_header.HeaderError) as raised:     # bare text has no folder to look in: expand() comes first
+        _header.parse('#include <stdint.h>\n#include "mpengine/core.h"\nint mp_f(void);\n')
+    assert "mpengine/core.h" in str(raised.value)
+
+
+def test_parser_ends_on_headers_that_include_each_other(tmp_path):
+    umbrella = _write(tmp_path, all='#include "other.h"\nint mp_a(void);\n#include "all.h"\n',
+                      other='#include "all.h"\nint mp_b(void);\n#include "other.h"\n')
+    assert list(_header.parse(_header.expand(umbrella)).signatures) == ["mp_b", "mp_a"]
+
+
 @pytest.mark.parametrize("text, names", [
     ("int mp_f(const float* x, unsigned n);", ["mp_f", "unsigned"]),             # parameter types outside the table
     ("int mp_f(long n);", ["mp_f", "long"]),
@@ -155,7 +206,7 @@ def test_parser_refuses_what_it_does_not_understand(text, names):
 
 
 def test_struct_layouts_match_the_c_compiler(tmp_path):
-    """sizeof and every offsetof of the nine descriptor structs, host cc against ctypes (the header compiles as C)."""
+    """sizeof and every offsetof of the nine descriptor structs, host cc against ctypes (the umbrella compiles as C)."""
     cc = shutil.which("cc") or shutil.which("gcc") or shutil.which("clang")
     if cc is None:
         pytest.skip("no host C compiler")

@@ -74,7 +74,7 @@ def test_abi_symbols_declared():
               "mp_edge_angle_grad_f32", "mp_spherical_basis_f32", "mp_spherical_basis_grad_f32",
               "mp_dimenet_triplet_f32", "mp_dimenet_triplet_grad_f32"):
         assert n in names
-    header = open(os.path.join(os.path.dirname(_ffi.__file__), "..", "include", "mpengine.h")).read()
+    header = _ffi.HEADER_TEXT
     assert "int mp_dimenet_triplet_f32(" in header and "#define MP_SBF_MAX_RADIAL 64" in header
 
 

@@ -2,13 +2,14 @@
 and the new ABI symbols.  Also pins the restatement the GPU tests measure against to a per-edge / per-graph NumPy loop.
 Runs without a GPU."""
 import ctypes
+import os
 
 import numpy as np
 import pytest
 import torch
 
 import hamnet_reference as href
-from gcnn_keras_amd import _ffi
+from gcnn_keras_amd import _ffi, _header
 from gcnn_keras_amd.layers.conv import hamnet_conv as hc
 from gcnn_keras_amd.layers.conv.mpnn_conv import GRUUpdate
 from gcnn_keras_amd.literature import HamNet
@@ -46,9 +47,13 @@ def test_hyper_model_default_is_the_references():
 
 
 def test_abi_declares_the_new_entry_points():
-    assert _ffi.model_symbols() == sorted(NEW_SYMBOLS)          # include/mpengine_hamnet.h, read behind mpengine.h
-    assert not set(NEW_SYMBOLS) & set(_ffi.declared_symbols())
+    family = os.path.join(os.path.dirname(_ffi.HEADER_PATH), "mpengine", "hamnet.h")   # one family under the umbrella
+    core = _header.parse(_header.expand(os.path.join(os.path.dirname(family), "core.h"))).signatures
+    declared = _header.parse(_header.expand(family)).signatures          # hamnet.h includes core.h, nothing else
+    assert sorted(set(declared) - set(core)) == sorted(NEW_SYMBOLS)
+    assert set(NEW_SYMBOLS) <= set(_ffi.declared_symbols())
     lib = _ffi.lib()
+    assert all(hasattr(lib, name) for name in NEW_SYMBOLS)
     assert all(getattr(lib, name).argtypes for name in NEW_SYMBOLS)
     assert lib.mp_hamnet_attend_f32.argtypes == [ctypes.c_int] + [ctypes.c_void_p] * 2 + [ctypes.c_int64, ctypes.c_void_p,
                                                                   ctypes.c_int64] + [ctypes.c_void_p] * 2 + \

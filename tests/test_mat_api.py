@@ -276,7 +276,7 @@ def test_refusals():
 
 # ------------------------------------------------------------------------------------------------ the ABI
 def test_new_symbol_and_constants_in_header_and_ffi():
-    text = open(os.path.join(ROOT, "include", "mpengine.h")).read()
+    text = _ffi.HEADER_TEXT
     assert re.search(r"\bint mp_mat_attention_f32\s*\(", text)
     assert "mp_mat_attention_f32" in _ffi.declared_symbols()
     for name in ("MP_MAT_RECV_TILE", "MP_MAT_SEND_TILE", "MP_MAT_TRAFO_NONE", "MP_MAT_TRAFO_EXP", "MP_MAT_TRAFO_SOFTMAX",

@@ -17,7 +17,7 @@ NEW_SYMBOLS = ("mp_dense_wgrad_f32", "mp_dense_wgrad_ws_bytes", "mp_embedding_gr
 
 
 def _header_text():
-    return open(os.path.join(ROOT, "include", "mpengine.h")).read()
+    return _ffi.HEADER_TEXT
 
 
 def test_new_symbols_in_header_and_ctypes_table():

@@ -102,7 +102,7 @@ def test_rounding_rule_is_float32_round_half_to_even(k):
 
 
 def test_new_symbols_in_header_and_ffi():
-    text = open(os.path.join(ROOT, "include", "mpengine.h")).read()
+    text = _ffi.HEADER_TEXT
     for name in ("mp_topk_workspace_bytes", "mp_topk_select_f32", "mp_topk_edges_count_i32", "mp_topk_edges_fill_f32",
                  "mp_adjacency_product_count_f32", "mp_adjacency_product_fill_f32", "mp_topk_invert_map_i64",
                  "mp_topk_unpool_f32"):
