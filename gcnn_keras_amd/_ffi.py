@@ -4,11 +4,11 @@ This is the only place where Python meets the engine: plain pointers and sizes c
 for device memory and streams only.  There is NO CPU fallback: if the shared library is missing or a tensor is
 not on a HIP device, the call fails loudly.
 
-Nothing of the ABI is written down here.  The umbrella header and the family headers it includes (include/mpengine/*.h)
-are read once at import (``_header.expand`` and ``_header.parse``, strict: a declaration it does not understand is an
-error) and give every ``MP_*`` constant as a module attribute, the descriptor structs as ``ctypes.Structure`` classes and
-the argument and return types of every entry point.  A new entry point is declared in a family header and defined in
-csrc/, nowhere else.
+Nothing of the ABI is written down here.  The umbrella header and the family headers it includes (include/mpengine/*.h),
+and behind them the family headers of ``PENDING_HEADERS``, are read once at import (``_header.expand`` and
+``_header.parse``, strict: a declaration it does not understand is an error) and give every ``MP_*`` constant as a
+module attribute, the descriptor structs as ``ctypes.Structure`` classes and the argument and return types of every
+entry point.  A new entry point is declared in a family header and defined in csrc/, nowhere else.
 """
 import ctypes
 import os
@@ -22,12 +22,22 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libmpengine.so")
 HEADER_PATH = os.path.join(_HERE, "..", "include", "mpengine.h")   # the umbrella over include/mpengine/*.h
 
-HEADER_TEXT = _header.expand(HEADER_PATH)   # the umbrella with every family header in place of its #include
-_ABI = _header.parse(HEADER_TEXT)
+# Family headers that wait for their #include line in the umbrella: read behind it with the same parser (their core.h is
+# the umbrella's, expanded once), their prototypes kept in a table of their own.  A header leaves this tuple when the
+# umbrella includes it; its prototypes then count among ``_SIGNATURES``.
+PENDING_HEADERS = ("mpengine/inorp.h",)
 
-globals().update(_ABI.constants)   # MP_OK, MP_EINVAL, MP_SUM, MP_ACT_*, MP_SCHNET_MAX_DEPTH, ...: every constant
-_SIGNATURES = _ABI.signatures      # name -> argtypes
-_RESTYPES = {name: restype for name, restype in _ABI.restypes.items() if restype is not c_int}   # int unless listed
+_seen = set()
+_UMBRELLA_TEXT = _header.expand(HEADER_PATH, _seen)   # the umbrella with every family header in place of its #include
+HEADER_TEXT = _UMBRELLA_TEXT + "".join(
+    "\n" + _header.expand(os.path.join(os.path.dirname(HEADER_PATH), _name), _seen) for _name in PENDING_HEADERS)
+_ABI = _header.parse(_UMBRELLA_TEXT)
+_FULL_ABI = _header.parse(HEADER_TEXT)
+
+globals().update(_FULL_ABI.constants)   # MP_OK, MP_EINVAL, MP_SUM, MP_ACT_*, MP_SCHNET_MAX_DEPTH, ...: every constant
+_SIGNATURES = _ABI.signatures      # name -> argtypes, of the umbrella
+_PENDING_SIGNATURES = {name: args for name, args in _FULL_ABI.signatures.items() if name not in _SIGNATURES}
+_RESTYPES = {name: restype for name, restype in _FULL_ABI.restypes.items() if restype is not c_int}   # int unless listed
 
 FilterTableLayout = _ABI.structs["mp_filter_table_layout"]
 SchnetForwardDesc = _ABI.structs["mp_schnet_forward_desc"]
@@ -59,8 +69,9 @@ class EngineError(RuntimeError):
 
 
 def declared_symbols():
-    """Names of every entry point declared under include/mpengine.h (checked by tests/test_abi.py)."""
-    return sorted(_SIGNATURES)
+    """Names of every entry point declared under include/mpengine.h and in the headers of ``PENDING_HEADERS`` (checked
+    by tests/test_abi.py)."""
+    return sorted(list(_SIGNATURES) + list(_PENDING_SIGNATURES))
 
 
 def lib():
@@ -75,7 +86,7 @@ def lib():
             raise EngineError("libmpengine.so not found at %s - build it with __graft_entry__.build() "
                               "(there is no CPU fallback)" % path)
         handle = ctypes.CDLL(path)
-        for name, argtypes in _SIGNATURES.items():
+        for name, argtypes in list(_SIGNATURES.items()) + list(_PENDING_SIGNATURES.items()):
             fn = getattr(handle, name, None)
             if fn is None:
                 if path == LIB_PATH:

@@ -540,9 +540,12 @@ class ActivationAdjoint(torch.autograd.Function):
 
 
 def _unbroadcast(g, shape):
-    """Sum ``g`` over the axes that were broadcast from ``shape`` (middle and / or last axis of the 3-D view)."""
+    """Sum ``g`` over the axes that were broadcast from ``shape`` (middle and / or last axis of the 3-D view, or the
+    rows of a 2-D operand of one row)."""
     if tuple(g.shape) == tuple(shape):
         return g
+    if g.dim() == 2 and len(shape) == 2 and int(shape[0]) == 1 and int(shape[1]) == int(g.shape[1]):
+        return _sum_rows(g.contiguous()).reshape(shape)   # one row against all rows (INorp's c (N, 1) x b2 (1, H2))
     if g.dim() != len(shape) or int(g.shape[0]) != int(shape[0]):
         raise NotImplementedError("gradient of a row-broadcast operand is outside the force path")
     r = int(g.shape[0])
@@ -1241,6 +1244,34 @@ class DirectedEdgeUpdate(torch.autograd.Function):
         want_b = ctx.needs_input_grad[3] and not _input_grads_only[0]
         h_bar, p, w_bar, b_bar = ctx.spec.grad(r, hv, y, kernel.detach(), g.contiguous(), want_h, want_w, want_b)
         return h_bar, (p if want_h0 else None), w_bar, b_bar, None
+
+
+# -------------------------------------------------------------------------------------------------------------- INorp
+# First-order rule of the folded INorp edge step (layers/conv/inorp_conv.py INorpEdgeStep; csrc/mp_inorp.hip).  The node
+# products in front of it and the Dense behind it are ``Dense`` rules on row-block views of the first kernel, so torch's
+# accumulation assembles the gradients of W1, b1, W2, b2 and of the nodes.
+
+class InorpEdge(torch.autograd.Function):
+    """``out[r] = pool over the edges of r of act(Pj[send] + Pi[recv] + edges Wc)`` (N, H1) (``spec``:
+    layers/conv/inorp_conv.py ``EdgeStepSpec``).  The forward is the fused route's launch and saves nothing edge-sized:
+    the backward recomputes the pre-activation (``mp_inorp_edge_grad_f32``) and returns ``Pj_bar``, ``Pi_bar``,
+    ``edges_bar`` and ``Wc_bar``, each only when asked.  First order."""
+
+    @staticmethod
+    def forward(ctx, pj, pi, edges, wc, spec):
+        pj, pi, edges, wc = pj.detach().contiguous(), pi.detach().contiguous(), edges.detach().contiguous(), wc.detach()
+        ctx.spec = spec
+        ctx.save_for_backward(pj, pi, edges, wc)
+        return spec.forward(pj, pi, edges, wc)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        pj, pi, edges, wc = ctx.saved_tensors
+        want = ctx.needs_input_grad
+        want_wc = want[3] and not _input_grads_only[0]
+        pj_bar, pi_bar, e_bar, wc_bar = ctx.spec.grad(pj, pi, edges, wc, g.contiguous(), want[0], want[2], want_wc)
+        return pj_bar, (pi_bar if want[1] else None), e_bar, wc_bar, None
 
 
 # -------------------------------------------------------------------------------------------------------------- MEGAN

@@ -1,0 +1,1 @@
+from . import INorp  # noqa: F401
