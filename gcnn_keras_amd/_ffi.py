@@ -26,17 +26,26 @@ HEADER_PATH = os.path.join(_HERE, "..", "include", "mpengine.h")   # the umbrell
 # the umbrella's, expanded once), their prototypes kept in a table of their own.  A header leaves this tuple when the
 # umbrella includes it; its prototypes then count among ``_SIGNATURES``.
 PENDING_HEADERS = ("mpengine/inorp.h",)
+# Family headers that came after it and wait the same way, read behind the pending ones; their prototypes are kept apart
+# in ``_FAMILY_SIGNATURES``: tests/test_inorp_api.py pins ``PENDING_HEADERS`` and ``_PENDING_SIGNATURES`` to INorp's own.
+FAMILY_HEADERS = ("mpengine/mxmnet.h",)
 
 _seen = set()
 _UMBRELLA_TEXT = _header.expand(HEADER_PATH, _seen)   # the umbrella with every family header in place of its #include
-HEADER_TEXT = _UMBRELLA_TEXT + "".join(
+_PENDING_TEXT = _UMBRELLA_TEXT + "".join(
     "\n" + _header.expand(os.path.join(os.path.dirname(HEADER_PATH), _name), _seen) for _name in PENDING_HEADERS)
+_FAMILY_TEXTS = {_name: _header.expand(os.path.join(os.path.dirname(HEADER_PATH), _name), _seen)
+                 for _name in FAMILY_HEADERS}
+HEADER_TEXT = _PENDING_TEXT + "".join("\n" + _text for _text in _FAMILY_TEXTS.values())
 _ABI = _header.parse(_UMBRELLA_TEXT)
+_PENDING_ABI = _header.parse(_PENDING_TEXT)
 _FULL_ABI = _header.parse(HEADER_TEXT)
 
 globals().update(_FULL_ABI.constants)   # MP_OK, MP_EINVAL, MP_SUM, MP_ACT_*, MP_SCHNET_MAX_DEPTH, ...: every constant
 _SIGNATURES = _ABI.signatures      # name -> argtypes, of the umbrella
-_PENDING_SIGNATURES = {name: args for name, args in _FULL_ABI.signatures.items() if name not in _SIGNATURES}
+_PENDING_SIGNATURES = {name: args for name, args in _PENDING_ABI.signatures.items() if name not in _SIGNATURES}
+_FAMILY_SIGNATURES = {name: args for name, args in _FULL_ABI.signatures.items()
+                      if name not in _SIGNATURES and name not in _PENDING_SIGNATURES}
 _RESTYPES = {name: restype for name, restype in _FULL_ABI.restypes.items() if restype is not c_int}   # int unless listed
 
 FilterTableLayout = _ABI.structs["mp_filter_table_layout"]
@@ -69,9 +78,9 @@ class EngineError(RuntimeError):
 
 
 def declared_symbols():
-    """Names of every entry point declared under include/mpengine.h and in the headers of ``PENDING_HEADERS`` (checked
-    by tests/test_abi.py)."""
-    return sorted(list(_SIGNATURES) + list(_PENDING_SIGNATURES))
+    """Names of every entry point declared under include/mpengine.h and in the headers of ``PENDING_HEADERS`` and
+    ``FAMILY_HEADERS`` (checked by tests/test_abi.py)."""
+    return sorted(list(_SIGNATURES) + list(_PENDING_SIGNATURES) + list(_FAMILY_SIGNATURES))
 
 
 def lib():
@@ -86,7 +95,8 @@ def lib():
             raise EngineError("libmpengine.so not found at %s - build it with __graft_entry__.build() "
                               "(there is no CPU fallback)" % path)
         handle = ctypes.CDLL(path)
-        for name, argtypes in list(_SIGNATURES.items()) + list(_PENDING_SIGNATURES.items()):
+        for name, argtypes in (list(_SIGNATURES.items()) + list(_PENDING_SIGNATURES.items())
+                               + list(_FAMILY_SIGNATURES.items())):
             fn = getattr(handle, name, None)
             if fn is None:
                 if path == LIB_PATH:

@@ -1186,6 +1186,48 @@ class EgnnEdge(torch.autograd.Function):
         return a_bar, b_bar, x_bar, None
 
 
+# ------------------------------------------------------------------------------------------------------------- MXMNet
+# First-order rules of csrc/mp_mxmnet.hip (layers/conv/mxmnet_conv.py).  The weights of the MXMNet layers stay frozen, so
+# there are no weight gradients; a backward in grad mode (a create_graph pass, i.e. a force loss) raises
+# NotImplementedError.
+
+class MxmEdge(torch.autograd.Function):
+    """The multiplex edge message of MXMNet: ``out`` (N, W) (pool epilogue, ``base`` (N, W) or None added) or ``y``
+    (E, W) (edge epilogue) of the node projections Pa, Pb (N, W) and the edge attributes a (E, Ka) (``spec``:
+    layers/conv/mxmnet_conv.py ``EdgeMessageSpec``, frozen weights); backward Pa_bar, Pb_bar, a_bar from the saved
+    pre-activation and gate, and g itself for ``base``."""
+
+    @staticmethod
+    def forward(ctx, pa, pb, a, base, spec):
+        ctx.spec = spec
+        out, ctx.z, ctx.l = spec.forward(pa.detach().contiguous(), pb.detach().contiguous(), a.detach().contiguous(),
+                                         None if base is None else base.detach().contiguous(), save=True)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        _first_order_only("the fused MXMNet edge message", "MXMNet")
+        g = g.contiguous()
+        pa_bar, pb_bar, a_bar = ctx.spec.grad(ctx.z, ctx.l, g, *ctx.needs_input_grad[:3])
+        return pa_bar, pb_bar, a_bar, (g if ctx.needs_input_grad[3] else None), None
+
+
+class MxmTriplet(torch.autograd.Function):
+    """The triplet pool of MXMLocalMP, out (E, W) of the edge messages x (E, W) and the basis rows s (T, W) (``spec``:
+    layers/conv/mxmnet_conv.py ``TripletPoolSpec``); backward x_bar and s_bar, each only when asked."""
+
+    @staticmethod
+    def forward(ctx, x, s, spec):
+        ctx.x, ctx.s, ctx.spec = x.detach().contiguous(), s.detach().contiguous(), spec
+        return spec.forward(ctx.x, ctx.s)
+
+    @staticmethod
+    def backward(ctx, g):
+        _first_order_only("the MXMLocalMP triplet pool", "MXMNet")
+        x_bar, s_bar = ctx.spec.grad(ctx.x, ctx.s, g, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        return x_bar, s_bar, None
+
+
 # ---------------------------------------------------------------------------------------------------------------- GRU
 class GRUCombine(torch.autograd.Function):
     """The GRUCell combine ``mp_gru_combine_f32`` of ``mx`` (R, 3U), ``mh`` (R, 3U) and the state ``h`` (R, U); backward

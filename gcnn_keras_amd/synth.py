@@ -876,3 +876,100 @@ def unet_params(model, seed=61, dense_scale=1.3):
             v = dense_scale * glorot_uniform(rng, shape[0], shape[-1], shape=shape)
         p["%03d/%s" % (i, name)] = np.asarray(v, dtype=np.float32)
     return p
+
+
+# ------------------------------------------------------------------------------------------------------------- MXMNet
+# The model section of the reference's MD17 MXMNet force-field runs (training/results/MD17Dataset/
+# MXMNet_EnergyForceModel/MXMNet_hyper_*.json): the energy model inside EnergyForceModel.  Local edges: the 3 A range
+# graph; global edges: the 5 A range graph.
+MXMNET_MD17 = {
+    "name": "MXMNetEnergy",
+    "inputs": [{"shape": [None], "name": "z", "dtype": "float32", "ragged": True},
+               {"shape": [None, 3], "name": "R", "dtype": "float32", "ragged": True},
+               {"shape": [None, 1], "name": "edge_weights", "dtype": "float32", "ragged": True},
+               {"shape": [None, 2], "name": "edge_indices", "dtype": "int64", "ragged": True},
+               {"shape": [None, 2], "name": "angle_indices_1", "dtype": "int64", "ragged": True},
+               {"shape": [None, 2], "name": "angle_indices_2", "dtype": "int64", "ragged": True},
+               {"shape": [None, 2], "name": "range_indices", "dtype": "int64", "ragged": True}],
+    "input_embedding": {"node": {"input_dim": 95, "output_dim": 128,
+                                 "embeddings_initializer": {"class_name": "RandomUniform",
+                                                            "config": {"minval": -1.7320508075688772,
+                                                                       "maxval": 1.7320508075688772}}},
+                        "edge": {"input_dim": 32, "output_dim": 128}},
+    "bessel_basis_local": {"num_radial": 16, "cutoff": 5.0, "envelope_exponent": 5},
+    "bessel_basis_global": {"num_radial": 16, "cutoff": 5.0, "envelope_exponent": 5},
+    "spherical_basis_local": {"num_spherical": 7, "num_radial": 6, "cutoff": 5.0, "envelope_exponent": 5},
+    "mlp_rbf_kwargs": {"units": 128, "activation": "swish"}, "mlp_sbf_kwargs": {"units": 128, "activation": "swish"},
+    "global_mp_kwargs": {"units": 128},
+    "local_mp_kwargs": {"units": 128, "output_units": 1, "output_kernel_initializer": "zeros"},
+    "use_edge_attributes": False, "depth": 6, "verbose": 10, "node_pooling_args": {"pooling_method": "sum"},
+    "output_embedding": "graph", "output_to_tensor": True, "use_output_mlp": False,
+    "output_mlp": {"use_bias": [True], "units": [1], "activation": ["linear"]},
+}
+
+
+def angle_pairs_ik_self(idx):
+    """Edge pairs ``(n, m)`` of kgcnn/graph/adj.py::get_angle_indices with ``edge_pairing="ik"`` and
+    ``allow_self_edges=True`` (MXMNet's second angle list): edge ``n = (i, j)`` pairs with every ``m = (i, k)``, no multi
+    or reverse edges, and with itself; ordered by n, then m."""
+    idx = np.asarray(idx, dtype=np.int64).reshape(-1, 2)
+    if len(idx) == 0:
+        return np.zeros((0, 2), np.int64)
+    a, b = idx[:, None, :], idx[None, :, :]
+    mask = b[..., 0] == a[..., 0]
+    mask &= (b[..., 0] != a[..., 0]) | (b[..., 1] != a[..., 1])      # multi edges
+    mask &= (b[..., 0] != a[..., 1]) | (b[..., 1] != a[..., 0])      # reverse edges
+    np.fill_diagonal(mask, True)                                     # self
+    n, m = np.nonzero(mask)
+    return np.stack([n, m], axis=-1).astype(np.int64)
+
+
+def mxmnet_batch(num_graphs=64, seed=2345, min_distance=0.9, sizes=None, local_distance=3.0, range_distance=5.0,
+                 sigma=1.7):
+    """A batch of MXMNet's seven inputs: molecules of ``sizes`` atoms (default 21, aspirin's elements cycled) drawn as
+    :func:`_molecule` draws them, the local edges within ``local_distance`` with both angle lists (``angle_indices_1``:
+    :func:`angle_pairs` "jk"; ``angle_indices_2``: :func:`angle_pairs_ik_self`), the global edges within
+    ``range_distance`` and uniform edge weights ``(E, 1)``; every index list is local to its molecule."""
+    rng = np.random.default_rng(seed)
+    sizes = [21] * num_graphs if sizes is None else list(sizes)
+    xs = [_molecule(rng, n, sigma, min_distance) for n in sizes]
+    es = [radius_graph(x, max_distance=local_distance, max_neighbours=10000).reshape(-1, 2) for x in xs]
+    rs = [radius_graph(x, max_distance=range_distance, max_neighbours=10000).reshape(-1, 2) for x in xs]
+    a1 = [angle_pairs(e, "jk") for e in es]
+    a2 = [angle_pairs_ik_self(e) for e in es]
+
+    def cat(parts, width):
+        return np.concatenate(parts, axis=0).reshape(-1, width).astype(np.int64)
+
+    b = {"node_number": np.concatenate([np.resize(ASPIRIN_Z, n) for n in sizes] or [np.zeros(0)]).astype(np.float32),
+         "node_coordinates": np.concatenate(xs, axis=0).reshape(-1, 3).astype(np.float32),
+         "edge_indices": cat(es, 2), "range_indices": cat(rs, 2),
+         "angle_indices_1": cat(a1, 2), "angle_indices_2": cat(a2, 2),
+         "node_splits": _splits(sizes), "edge_splits": _splits([len(e) for e in es]),
+         "range_splits": _splits([len(r) for r in rs]), "angle_splits_1": _splits([len(a) for a in a1]),
+         "angle_splits_2": _splits([len(a) for a in a2])}
+    b["edge_weights"] = np.ones((len(b["edge_indices"]), 1), dtype=np.float32)
+    return b
+
+
+def mxmnet_params(model, seed=17, dense_scale=0.6):
+    """Random weights for a built MXMNet ``model`` in ``model.weights`` order: Dense kernels Glorot-uniform times
+    ``dense_scale`` (the output kernels too, which ``output_kernel_initializer="zeros"`` would leave at 0 and the output
+    a constant), biases in +-0.1, the embedding in +-sqrt(3), Bessel frequencies ``pi * (1..R)``.  The local message
+    passing sums over edges and triplets without a normalisation: at scale 1 the node states of a 9-atom molecule grow
+    by orders of magnitude per block, and float32 forces lose their digits whoever computes them."""
+    rng = np.random.default_rng(seed)
+    p = {}
+    for i, (name, t) in enumerate(model.weights):
+        shape = tuple(int(s) for s in t.shape)
+        leaf = name.rsplit("/", 1)[-1]
+        if leaf == "embeddings":
+            v = rng.uniform(-np.sqrt(3.0), np.sqrt(3.0), size=shape)
+        elif leaf == "frequencies":
+            v = np.pi * np.arange(1, shape[0] + 1)
+        elif leaf == "bias":
+            v = rng.uniform(-0.1, 0.1, size=shape)
+        else:
+            v = dense_scale * glorot_uniform(rng, shape[0], shape[-1], shape=shape)
+        p["%03d/%s" % (i, name)] = np.asarray(v, dtype=np.float32)
+    return p
